@@ -8,7 +8,19 @@ walk_length 80, 10 walks per node.  One "step" = one pass of the hot path over
 one batch: 10 walks from every vertex (6.47M walks, ~5.1e8 walk-steps) written
 to HBM, per rank.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,4,5}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,4,5}] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and nothing else: it builds the
+graph, prepares the sampler, warms up, times the K steps and prints the result
+line (`value`, `ms_per_step` = milliseconds per timed step, and the roofline
+derived from the HIP events of those same steps).  Everything that takes runs
+of its own is behind `--full`: the secondary workloads, the CPU baselines, the
+edge-following spot check of the emitted walks, the stream-copy bandwidth, the
+rejection sampler's end-to-end line and, on one GPU, the host-shard lines.
+`--dump-outputs DIR` writes what the last timed step returned to its caller as
+DIR/<name>.npy (float64; a fixed, seeded sample of the rows, at most 64 MB in
+all): with the same arguments the inputs and the sampled rows are identical
+from run to run, so two builds can be compared output for output.
 
 Ranks.  `--gpus N > 1` without WORLD_SIZE in the environment: bench.py starts
 `python -m torch.distributed.run --nproc-per-node N` as a CHILD process (before
@@ -25,7 +37,7 @@ checks the gathered block of the last rank byte-for-byte against its own
 recomputation of that block.
 
 Configs (BASELINE.json):
-  2  headline above; secondaries (1 GPU): TopSim on lshrank blog (config 3),
+  2  headline above; secondaries (`--full`, 1 GPU): TopSim on lshrank blog (config 3),
      the north_star 10M/100M graph at the bench's p/q and at p=q=1, config 4 and
      config 5 on one GPU, naive SimRank on blog.  At world > 1 the secondaries
      are configs 4 and 5, sharded.
@@ -35,7 +47,7 @@ Configs (BASELINE.json):
      SAMPLE 1000): all non-isolated sources split over the ranks (strong
      scaling); value = pair-updates/s.
 
-Also in the JSON line:
+Also in the JSON line (cpu_baseline and the stream copy with `--full` only):
   roofline      36 algorithmic bytes per walk-step / kernel time
                 (HIP events on the launch stream); traffic = HBM bytes per launch
                 from the committed rocprofv3 PMC summary of this exact library
@@ -130,6 +142,11 @@ def parse(argv):
                     help="config 5 graph size (BASELINE: 10M vertices, 10 R-MAT lines per vertex); smaller for tests")
     ap.add_argument("--plumbing-check", action="store_true",
                     help="ranks + collectives with synthetic rows, no GPU work, no throughput")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: secondary workloads, CPU baselines, the walk "
+                         "spot check, stream copy, the rejection sampler's end-to-end line, 1-GPU host-shard lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (a fixed, seeded sample of rows) as DIR/<name>.npy")
     a = ap.parse_args(argv)
     cfg = {2: dict(scale=20, p=0.25, q=4.0, num_walks=10, mode="auto"),
            4: dict(scale=24, p=1.0, q=0.5, num_walks=10, mode="rejection"),
@@ -547,6 +564,30 @@ def gather_rows_timing(R, args, tensors, run=None):
             "check_blocks_match_sender_checksums": bool(allok)}
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: float64 bytes written per run (the limit is 64 MB)
+
+
+def dump_outputs(R, args, arrays, valid):
+    """--dump-outputs DIR: the rows of `arrays` (name -> tensor, one row per
+    walk or source, as the timed path's caller holds them after the last timed
+    step) written by rank 0 as DIR/<name>.npy in float64 (exact for int32 ids).
+    Outputs above DUMP_BYTES are sampled: the same sorted row subset, drawn
+    from --seed, of every array, its indices in DIR/rows.npy."""
+    if not args.dump_outputs or R.rank != 0:
+        return
+    import numpy as np
+    torch = R.torch
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    per_row = 8 * (1 + sum(t.numel() // max(t.shape[0], 1) for t in arrays.values()))
+    k = max(0, min(valid, DUMP_BYTES // per_row))
+    rows = np.arange(valid, dtype=np.int64) if k == valid else \
+        np.sort(np.random.default_rng(args.seed).choice(valid, size=k, replace=False))
+    idx = torch.as_tensor(rows, device=R.dev)
+    np.save(os.path.join(args.dump_outputs, "rows.npy"), rows.astype(np.float64))
+    for name, t in arrays.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), t[idx].cpu().numpy().astype(np.float64))
+
+
 # ---- workloads -----------------------------------------------------------------
 def stream_copy_gbps(R, nbytes=4 << 30, reps=5):
     """Achievable HBM bandwidth on this box: a device-to-device copy of
@@ -601,6 +642,7 @@ def walk_headline(R, args):
             out[:cnt_w].copy_(synth(first(i), cnt_w))
         step.recompute = synth
         el, _ = time_steps(R, step, args.steps, args.warmup, events=False)
+        dump_outputs(R, args, {"walks": out}, cnt_w)
         steps_total = int(R.allreduce([args.steps * cnt_w * (L - 1)], "sum", torch.int64)[0])
         res = {"value": None, "walk_steps": steps_total, "seconds": el, "n": n, "nnz": None, "mode": "plumbing",
                "B": B, "walks_per_step": total}
@@ -686,6 +728,7 @@ def walk_headline(R, args):
     torch.cuda.synchronize()
     cnt.zero_()
     el, k_avg_ms = time_steps(R, step, args.steps, 0)
+    dump_outputs(R, args, {"walks": out}, cnt_w)  # before anything below walks into `out` again
     steps_local, trials_local = int(cnt[0].item()), int(cnt[1].item())
     steps_total, trials_total = (int(x) for x in R.allreduce([steps_local, trials_local], "sum", torch.int64))
     value = steps_total / el
@@ -702,8 +745,8 @@ def walk_headline(R, args):
     line_rate["ceiling_frac_at_one_request_per_step"] = \
         BYTES_PER_STEP * line_rate["calibrated_peak_lines_per_s"] / (HBM_PEAK_GBS * 1e9)
 
-    # ---- parity spot check (cheap): every step of a sample follows an edge ----
-    if rank == 0:
+    # ---- parity spot check (--full): every step of a sample follows an edge ----
+    if rank == 0 and args.full:
         csr = G.export_csr()
         smp = out[:2000].cpu().numpy()
         offs, nbrs = csr["offsets"], csr["nbrs"]
@@ -743,9 +786,9 @@ def walk_headline(R, args):
         res["host_shard"] = walks_to_host(R, args, G, L, first, cnt_w, args.steps, recompute, steps_total)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline_walks(G.export_csr(), args.p, args.q, args.seed, L, 0, args.cpu_seconds)
-    if rank == 0:
+    if rank == 0 and args.full:
         res["copy_gbps"] = stream_copy_gbps(R)
-    if mode == "bitset" and world == 1:
+    if mode == "bitset" and world == 1 and args.full:
         # the same BASELINE pass end to end with the plain rejection sampler
         # (16 B slot entries + neighbour hash, no per-edge tables): the
         # sampler a one-shot run should pick is the faster end to end
@@ -1067,7 +1110,7 @@ def p10m_graph(R, args):
     return _P10M_GRAPH[key]
 
 
-def run_topsim(R, args, name, sample=None, step=None, stride=1, cpu_seconds=None, cpu=True):
+def run_topsim(R, args, name, sample=None, step=None, stride=1, cpu_seconds=None, cpu=True, dump=False):
     """TopSim_singleSample: lshrank graphs (config 3; every rank all sources;
     default SAMPLE / STEP from --topsim-sample / --topsim-step) or P10M
     (config 5 at SAMPLE 1000 / STEP 3, or the SURVEY §8d stretch SAMPLE 10000
@@ -1098,6 +1141,8 @@ def run_topsim(R, args, name, sample=None, step=None, stride=1, cpu_seconds=None
             ids[:len(srcs)] = ((s_ * K + torch.arange(K)) % nsrc_all).to(torch.int32)
             sc[:len(srcs)] = s_.to(torch.float64) + torch.arange(K, dtype=torch.float64) / K
         synth()
+        if dump:
+            dump_outputs(R, args, {"topk_ids": ids, "topk_scores": sc}, len(srcs))
         g = gather_rows_timing(R, args, [ids, sc], run=synth) if world > 1 else None
         host = None
         if args.host_shard == "on" or (args.host_shard == "auto" and world > 1):
@@ -1161,6 +1206,8 @@ def run_topsim(R, args, name, sample=None, step=None, stride=1, cpu_seconds=None
         if ev is not None:
             ev[1].record(stream)
     tel, kms = time_steps(R, tstep, 1, 0)
+    if dump:
+        dump_outputs(R, args, {"topk_ids": ids, "topk_scores": sc, "sources": src.unsqueeze(1)}, nloc)
     timed = dict(last)
     kattrs = ts_kernel_attrs(h) if nloc else None
     ext_l, upd_l = int(st[0].item()), int(st[1].item())
@@ -1370,10 +1417,15 @@ def main(argv):
         log(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
         return 2
     R = Ranks(args)
+    if not args.full:  # the plain run: the headline's own steps only
+        args.secondary = "none"
+        args.no_cpu_baseline = True
+        if R.world == 1 and args.host_shard == "auto":
+            args.host_shard = "off"
     secondary = {}
     cpu = None
     if args.config == 5:
-        h = run_topsim(R, args, "p10m")
+        h = run_topsim(R, args, "p10m", dump=True)
         value, metric, unit = h["value"], h["metric"], h["unit"]
         head = h
     else:
@@ -1482,7 +1534,7 @@ def main(argv):
                 res["allgather_all_ranks_ok"] = head["allgather_all_ranks_ok"]
             if "host_shard" in head:
                 res["host_shard"] = head["host_shard"]
-        ref = reference_cpu_fixture()
+        ref = reference_cpu_fixture() if args.full else None
         if ref and not R.plumbing:
             res["reference_cpu_context"] = {"file": "profiles/cpu_reference_node2vec.json",
                                             "summary": ref.get("summary")}

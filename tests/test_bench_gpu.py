@@ -97,7 +97,7 @@ def test_bench_config3_sweep_small():
     moreno and arxiv: one point per (graph, SAMPLE), each naming the kernel it
     dispatched with its registers / scratch, the timed dispatch's ordinal for
     the PMC passes, and a CPU oracle baseline where asked."""
-    rc, res, err = _run(["--scale", "10", "--steps", "1", "--warmup", "0", "--no-walk10m", "--no-simrank",
+    rc, res, err = _run(["--full", "--scale", "10", "--steps", "1", "--warmup", "0", "--no-walk10m", "--no-simrank",
                          "--no-rmat24", "--no-p10m", "--no-p10m-stretch", "--no-arxiv", "--topsim-graphs", "moreno",
                          "--config3-graphs", "moreno,arxiv", "--config3-samples", "1000,5000",
                          "--config3-cpu-samples", "1000", "--config3-cpu-seconds", "0.5", "--cpu-seconds", "0.5"])
@@ -117,3 +117,27 @@ def test_bench_config3_sweep_small():
     assert pts[3]["kernel"] == "k_topsim_2wg<5, 2>"  # arxiv 5000: W/E < 16 keeps the unpipelined kernel
     # the moreno line of secondary.topsim is NOT a second run of the sweep's point at another SAMPLE
     assert res["secondary"]["topsim"]["config"]["sample"] == 10000
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_last_step(tmp_path, gw, oracle):
+    """A plain run times its steps and nothing else (no secondary, CPU
+    baseline, stream copy or second sampler), and --dump-outputs writes the
+    last timed step's walks as float64: every row (the output is small), equal
+    to the CPU oracle's walks of that step's global walk block."""
+    import numpy as np
+    steps = 3
+    rc, res, err = _run(["--scale", "10", "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert rc == 0, err[-3000:]
+    assert res["steps"] == steps and res["value"] > 0
+    assert res["ms_per_step"] > 0 and res["walk_steps"] == steps * res["roofline"]["units_per_launch"]
+    assert res["secondary"] is None and res["cpu_baseline"] is None and res["summary"] is None
+    assert "end_to_end_rejection" not in res and res["roofline"]["stream_copy_GBps"] is None
+    walks, rows = np.load(tmp_path / "walks.npy"), np.load(tmp_path / "rows.npy")
+    B = res["config"]["walks_per_step"]
+    assert walks.dtype == np.float64 and walks.shape == (B, 80)
+    assert np.array_equal(rows, np.arange(B))
+    G = gw.GWGraph.rmat(10, 16, 0.57, 0.19, 0.19, 42)
+    assert res["sampler"] == "bitset"
+    ref, _, _ = oracle.walks_bitset(G.export_csr(), 0.25, 4.0, 42, 80, (steps - 1) * B, B, nthreads=8)
+    assert np.array_equal(walks, ref)

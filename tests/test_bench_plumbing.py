@@ -100,3 +100,30 @@ def test_bench_rank_count_mismatch_is_refused():
     rc, res, err = _run(["--gpus", "2", "--plumbing-check"], {"WORLD_SIZE": "1"}, timeout=120)
     assert rc == 2 and res is None
     assert "WORLD_SIZE=1" in err
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_of_the_last_step(tmp_path):
+    """--dump-outputs on an output larger than the dump limit: float64 files of
+    at most 64 MB in all, a sorted duplicate-free row sample that is the same
+    in a second run with the same arguments, and rows that are the last timed
+    step's rows (--plumbing-check row w = (w*L + t) mod (2^31 - 1))."""
+    import numpy as np
+    steps, warmup, scale, L, nw = 2, 1, 14, 80, 10
+    B = nw * (1 << scale)
+    got = []
+    for d in ("a", "b"):
+        rc, res, err = _run(["--gpus", "1", "--plumbing-check", "--scale", str(scale), "--steps", str(steps),
+                             "--warmup", str(warmup), "--dump-outputs", str(tmp_path / d)])
+        assert rc == 0, err[-2000:]
+        assert res["steps"] == steps and res["walk_steps"] == steps * B * (L - 1) and res["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["rows.npy", "walks.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 64 << 20
+        got.append((np.load(tmp_path / d / "rows.npy"), np.load(tmp_path / d / "walks.npy")))
+    rows, walks = got[0]
+    assert rows.dtype == np.float64 and walks.dtype == np.float64
+    assert B * L * 8 > 64 << 20 and 50_000 < len(rows) < B  # sampled, and not a token sample
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < B
+    assert np.array_equal(rows, got[1][0]) and np.array_equal(walks, got[1][1])
+    w = (steps + warmup - 1) * B + rows.astype(np.int64)[:, None]  # the last timed step's global walk block
+    assert np.array_equal(walks, (w * L + np.arange(L)) % (2**31 - 1))

@@ -11,15 +11,15 @@
 # segfault or time-out).  Outputs: gpurun_out/<step>_<TAG>.*
 #   tests    python -m pytest -m gpu (TEST_ARGS: files, default the whole GPU suite; TEST_K: a -k expression)
 #   smoke    __graft_entry__.smoke()
-#   bench    python bench.py $BENCH_ARGS                      -> bench_<TAG>.json
-#   kt       rocprofv3 --kernel-trace --stats of bench.py --no-cpu-baseline $BENCH_ARGS
+#   bench    python bench.py --full $BENCH_ARGS               -> bench_<TAG>.json
+#   kt       rocprofv3 --kernel-trace --stats of bench.py --full --no-cpu-baseline $BENCH_ARGS
 #            (+ tools/kt_summary.py)                          -> kt_<TAG>/
 #   pmc      three separate --pmc passes (FETCH_SIZE; WRITE_SIZE;
 #            TCC_EA0_RDREQ/HIT/MISS) on the same command, for
 #            tools/pmc_summary.py                             -> pmc{1,2,3}_<TAG>/
 #   counters one --pmc pass per group of PMC_GROUPS (groups separated by ';',
 #            e.g. "SQ_WAVES SQ_WAIT_ANY SQ_INSTS_VALU;TCP_TCC_READ_REQ_sum") on
-#            bench.py --no-cpu-baseline $BENCH_ARGS, kernels matching $KRE;
+#            bench.py --full --no-cpu-baseline $BENCH_ARGS, kernels matching $KRE;
 #            per-kernel means printed by tools/pmc_lines.py   -> cnt<i>_<TAG>/
 #   ab       tools/ab_inproc.py $AB_ARGS (walk-kernel library / knob A/B in one
 #            process)                                         -> ab_<TAG>.jsonl
@@ -56,12 +56,12 @@ for step in "$@"; do
       timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$log" 2>&1 || step_fail smoke $? "$log"
       echo "STEP_OK smoke" ;;
     bench)
-      timeout -k 10 "$T_STEP" python bench.py $BENCH_ARGS > "$O/bench_$TAG.json" 2> "$O/bench_$TAG.err" ||
+      timeout -k 10 "$T_STEP" python bench.py --full $BENCH_ARGS > "$O/bench_$TAG.json" 2> "$O/bench_$TAG.err" ||
         step_fail bench $? "$O/bench_$TAG.err"
       echo "STEP_OK bench: $(python -c "import json;d=json.load(open('$O/bench_$TAG.json'));print(d['value'], d['ms_per_step'], d['roofline']['frac'])")" ;;
     kt)
       timeout -k 10 "$T_STEP" rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_$TAG" -o kt -- \
-        python bench.py --no-cpu-baseline $BENCH_ARGS > "$O/kt_$TAG.json" 2> "$O/kt_$TAG.err" ||
+        python bench.py --full --no-cpu-baseline $BENCH_ARGS > "$O/kt_$TAG.json" 2> "$O/kt_$TAG.err" ||
         step_fail kt $? "$O/kt_$TAG.err"
       python tools/kt_summary.py "$O/kt_$TAG/kt_kernel_trace.csv" "$O/kt_$TAG/kernel_dispatch_summary.json" > /dev/null || true
       python tools/kt_lines.py "$O/kt_$TAG/kt_kernel_trace.csv" "$O/kt_$TAG.json" "$O/kt_$TAG/kt_lines.json" > /dev/null || true
@@ -71,7 +71,7 @@ for step in "$@"; do
       for counters in "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_RDREQ_sum TCC_HIT_sum TCC_MISS_sum"; do
         i=$((i + 1))
         timeout -k 10 "$T_STEP" rocprofv3 --pmc $counters --kernel-include-regex "$KRE" --output-format csv \
-          -d "$O/pmc${i}_$TAG" -o pmc -- python bench.py --no-cpu-baseline $BENCH_ARGS \
+          -d "$O/pmc${i}_$TAG" -o pmc -- python bench.py --full --no-cpu-baseline $BENCH_ARGS \
           > "$O/pmc${i}_$TAG.json" 2> "$O/pmc${i}_$TAG.err" || step_fail "pmc$i" $? "$O/pmc${i}_$TAG.err"
         echo "STEP_OK pmc$i"
       done ;;
@@ -81,7 +81,7 @@ for step in "$@"; do
       for counters in "${groups[@]}"; do
         i=$((i + 1))
         timeout -k 10 "$T_STEP" rocprofv3 --pmc $counters --kernel-include-regex "$KRE" --output-format csv \
-          -d "$O/cnt${i}_$TAG" -o pmc -- python bench.py --no-cpu-baseline $BENCH_ARGS \
+          -d "$O/cnt${i}_$TAG" -o pmc -- python bench.py --full --no-cpu-baseline $BENCH_ARGS \
           > "$O/cnt${i}_$TAG.json" 2> "$O/cnt${i}_$TAG.err" || step_fail "counters$i" $? "$O/cnt${i}_$TAG.err"
         python tools/pmc_lines.py "$O/cnt${i}_$TAG" "$O/cnt${i}_$TAG.json" || true
         echo "STEP_OK counters$i ($counters)"
