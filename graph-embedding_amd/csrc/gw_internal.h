@@ -133,6 +133,7 @@ struct gw_topsim_ws {
   unsigned int* src_counter = nullptr;  // work queue head
   int* error_flag = nullptr;      // capacity overflow
   char kernel[32] = {0};          // the kernel this workspace launches (gw_topsim_kernel)
+  int last_launches = 0;          // kernel launches of the last gw_dev_topsim call (gw_topsim_last_launches)
 };
 
 // TopSim sparse rows (gw_topsim_sparse): per source r, row_len[r] nonzero

@@ -1047,6 +1047,8 @@ __device__ __forceinline__ void topsim_body(const TsArgs& A) {
           s_co[1] = A.sample;
           s_nspawn = 1;
           s_nwalk = A.sample;
+        } else {
+          my_walk += A.sample;  // an isolated root still makes its SAMPLE empty walks (:55-72): counted as walkers
         }
       }
       __syncthreads();
@@ -2310,6 +2312,7 @@ int gw_dev_topsim(gw_graph* g, int variant, int sample, int step, double C, uint
     int rc = gw_dev_topsim_prepare(g, variant, sample, step, std::max(topk, t.topk > 0 ? t.topk : topk));
     if (rc != GW_OK) return rc;
   }
+  t.last_launches = 0;
   if (nsrc <= 0) return GW_OK;
   GW_HIP_TRY(hipSetDevice(g->device));
   hipStream_t s = (hipStream_t)stream;
@@ -2394,6 +2397,7 @@ int gw_dev_topsim(gw_graph* g, int variant, int sample, int step, double C, uint
       g->err = std::string("k_topsim launch: ") + hipGetErrorString(e);
       return GW_ERR_DEVICE;
     }
+    t.last_launches = pass + 1;
     GW_HIP_TRY(hipMemcpyAsync(&flag, t.error_flag, sizeof(int), hipMemcpyDeviceToHost, s));
     GW_HIP_TRY(hipStreamSynchronize(s));
     if (!(flag & 8) || A.app_cap == 0) break;
@@ -2428,6 +2432,10 @@ int gw_dev_topsim(gw_graph* g, int variant, int sample, int step, double C, uint
 
 extern "C" const char* gw_topsim_kernel(const gw_graph* g) {
   return g ? g->ts.kernel : "";
+}
+
+extern "C" int gw_topsim_last_launches(const gw_graph* g) {
+  return g ? g->ts.last_launches : 0;
 }
 
 extern "C" int gw_topsim_kernel_attrs(gw_graph* g, int32_t* vgprs, int32_t* scratch_bytes, int32_t* lds_bytes) {

@@ -279,6 +279,12 @@ int gw_topsim_prepare(gw_graph* g, int variant, int sample, int step, int topk);
  * the first gw_topsim_prepare / gw_topsim* call).  Diagnostic: the choice
  * depends on V, SAMPLE and STEP (no reference counterpart).                 */
 const char* gw_topsim_kernel(const gw_graph* g);
+/* Kernel launches the last gw_topsim / gw_topsim_dense / gw_topsim_sparse
+ * call on this handle made: 1, or 2 when a heavy source's partition filled
+ * and the launch was re-run without the append path (0 before the first call
+ * and after a call with no sources).  The host-buffer forms (gw_topsim_host,
+ * gw_topsim_write_text) report their last batch.                            */
+int gw_topsim_last_launches(const gw_graph* g);
 /* Registers per lane, private segment (scratch) bytes per lane and LDS bytes
  * per workgroup (static + dynamic) of that kernel (hipFuncGetAttributes).   */
 int gw_topsim_kernel_attrs(gw_graph* g, int32_t* vgprs, int32_t* scratch_bytes, int32_t* lds_bytes);

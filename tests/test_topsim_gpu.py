@@ -335,6 +335,7 @@ def test_topsim_stretch_heavy_sources_sparse_and_dense_rows(gw, oracle):
         st = torch.zeros(4, dtype=torch.int64, device="cuda")
         rc = Cl.lib().gw_topsim_sparse(g.handle, 0, sample, step, 0.6, 42, Cl.ptr(src), len(pick), capacity,
                                        Cl.ptr(b), Cl.ptr(ln), Cl.ptr(ids), Cl.ptr(sc), Cl.ptr(used), Cl.ptr(st), None)
+        assert Cl.lib().gw_topsim_last_launches(g.handle) == 1  # no partition overflow: no re-run
         return rc, b.cpu().numpy(), ln.cpu().numpy(), ids.cpu().numpy(), sc.cpu().numpy(), int(used.cpu()[0]), \
             st.cpu().numpy()
 
@@ -354,6 +355,7 @@ def test_topsim_stretch_heavy_sources_sparse_and_dense_rows(gw, oracle):
     st2 = torch.zeros(4, dtype=torch.int64, device="cuda")
     Cl.check(Cl.lib().gw_topsim_dense(g.handle, 0, sample, step, 0.6, 42, Cl.ptr(src), len(pick), Cl.ptr(rows),
                                       Cl.ptr(st2), None), g.handle)
+    assert Cl.lib().gw_topsim_last_launches(g.handle) == 1
     R = rows.cpu().numpy()
     np.testing.assert_allclose(R, ref, rtol=1e-12, atol=0)
     assert np.array_equal(R > 0, ref > 0)
@@ -385,6 +387,7 @@ def test_topsim_partition_overflow_reruns_without_append(gw, oracle):
     st = torch.full((4,), 7, dtype=torch.int64, device="cuda")  # accumulated onto, as the caller's counters
     Cl.check(Cl.lib().gw_topsim(g.handle, 0, sample, step, 0.6, 42, Cl.ptr(src), len(pick), K, Cl.ptr(ids),
                                 Cl.ptr(sc), Cl.ptr(st), None), g.handle)
+    assert Cl.lib().gw_topsim_last_launches(g.handle) == 2  # flag 8 fired: the launch and its re-run
     oi, osc, ost = oracle.topsim_topk(offs, nbrs, 0, sample, step, K, C=0.6, seed=42, sources=pick, nthreads=8)
     stg = st.cpu().numpy()
     assert int(stg[0]) == 7 + ost["extensions"] and int(stg[1]) == 7 + ost["pair_updates"]
@@ -401,6 +404,7 @@ def test_topsim_partition_overflow_reruns_without_append(gw, oracle):
     st2 = torch.zeros(4, dtype=torch.int64, device="cuda")
     Cl.check(Cl.lib().gw_topsim_sparse(g.handle, 0, sample, step, 0.6, 42, Cl.ptr(src), 4, cap, Cl.ptr(b), Cl.ptr(ln),
                                        Cl.ptr(sid), Cl.ptr(ssc), Cl.ptr(used), Cl.ptr(st2), None), g.handle)
+    assert Cl.lib().gw_topsim_last_launches(g.handle) == 2
     B, LN, I, S = b.cpu().numpy(), ln.cpu().numpy(), sid.cpu().numpy(), ssc.cpu().numpy()
     assert int(used.cpu()[0]) == int(LN.sum()) and int(st2[1]) == rst["pair_updates"]
     for r in range(4):
