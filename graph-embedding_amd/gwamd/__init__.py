@@ -4,6 +4,9 @@ Host-side mirror of the reference interfaces over the libgraphwalk C ABI
 (include/graphwalk.h):
 
 * `gwamd.node2vec`  — node2vec/src/node2vec.py (Graph, alias_setup, alias_draw)
+* `gwamd.embed`     — learn_embeddings (node2vec/src/main.py:92-101): skip-gram /
+                      negative-sampling training on the device-resident walks,
+                      save_word2vec_format
 * `gwamd.topsim`    — DeepSim/TopSimAll structures.Graph, TopSim_singleSample,
                       TopSim_Enumerate, SingleRandomWalk, SimRank (naive),
                       Print.printByOrder/printByOrderAll,

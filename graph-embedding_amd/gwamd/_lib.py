@@ -84,6 +84,26 @@ class Options(ctypes.Structure):
                 ("reserved0", ctypes.c_int32)]
 
 
+class SgnsParams(ctypes.Structure):
+    """gw_sgns_params_t (include/graphwalk.h); struct_size is filled in by default."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("dim", ctypes.c_int32), ("window", ctypes.c_int32),
+                ("negative", ctypes.c_int32), ("epochs", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+                ("alpha", ctypes.c_double), ("min_alpha", ctypes.c_double), ("sample", ctypes.c_double),
+                ("seed", ctypes.c_uint64)]
+
+    def __init__(self, dim=128, window=5, negative=5, epochs=5, alpha=0.025, min_alpha=0.0001, sample=1e-3, seed=0):
+        super().__init__(ctypes.sizeof(SgnsParams), dim, window, negative, epochs, 0, alpha, min_alpha, sample, seed)
+
+
+class SgnsStats(ctypes.Structure):
+    """gw_sgns_stats_t."""
+    _fields_ = [("tokens_kept", ctypes.c_int64), ("pairs", ctypes.c_int64), ("negatives", ctypes.c_int64),
+                ("negatives_centre", ctypes.c_int64), ("targets_clipped", ctypes.c_int64)]
+
+    def as_tuple(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_)
+
+
 P = ctypes.c_void_p
 I32 = ctypes.c_int32
 I64 = ctypes.c_int64
@@ -151,6 +171,18 @@ SIGNATURES = {
     "gw_write_sim_text_topk": (ctypes.c_int, [CP, P, P, P, I64, ctypes.c_int, CP, ctypes.c_int]),
     "gw_write_sim_text_sparse": (ctypes.c_int, [CP, P, P, P, P, P, I64, I64, ctypes.c_int, CP, ctypes.c_int]),
     "gw_write_sim_text_cachemap": (ctypes.c_int, [CP, P, P, P, P, I64, ctypes.c_int, ctypes.c_int, CP]),
+    "gw_sgns_create": (ctypes.c_int, [ctypes.c_int, I64, ctypes.POINTER(SgnsParams), PP]),
+    "gw_sgns_free": (ctypes.c_int, [P]),
+    "gw_sgns_last_error": (CP, [P]),
+    "gw_sgns_build_vocab": (ctypes.c_int, [P, P, I64, ctypes.c_int]),
+    "gw_sgns_train": (ctypes.c_int, [P, P, I64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.POINTER(SgnsStats), P]),
+    "gw_sgns_export": (ctypes.c_int, [P, P, P, P]),
+    "gw_sgns_sampler_export": (ctypes.c_int, [P, P, P, P]),
+    "gw_sgns_vectors_dev": (ctypes.c_int, [P, PP, PI64]),
+    "gw_sgns_auto_concurrency_for": (ctypes.c_int, [P, I64, PI32]),
+    "gw_sgns_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, PI32, PI32, PI32]),
+    "gw_write_word2vec_text": (ctypes.c_int, [CP, P, P, P, I64, ctypes.c_int]),
     "gw_comm_unique_id": (ctypes.c_int, [P]),
     "gw_comm_init": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, PP]),
     "gw_comm_allgather": (ctypes.c_int, [P, P, P, I64, ctypes.c_int, P]),
@@ -178,11 +210,12 @@ def lib():
     return _lib
 
 
-def check(rc, handle=None):
+def check(rc, handle=None, sgns=None):
+    """Raise for a failing status; `handle` a gw_graph, `sgns` a gw_sgns (for the message)."""
     if rc == GW_OK:
         return
     L = lib()
-    msg = L.gw_last_error(handle).decode(errors="replace")
+    msg = (L.gw_sgns_last_error(sgns) if sgns is not None else L.gw_last_error(handle)).decode(errors="replace")
     if rc == GW_ERR_INVALID:
         raise ValueError(msg)
     if rc == GW_ERR_IO:

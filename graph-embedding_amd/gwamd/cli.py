@@ -6,10 +6,14 @@
 main.py:20-73 flags are accepted with the same names, defaults and quirks
 (`--delimiter` defaults to ',' (:59); `--unweighted`/`--undirected` write to
 their own dests and never clear `weighted`/`directed` (:64, :69)).
-The embedding flags (--output, --dimensions, --window-size, --iter,
---workers) belong to gensim's Word2Vec (main.py:92-101), which is out of
-scope: they are accepted and ignored.  Walks are written in DeepSim's
-save_list format (DeepSim/src/main.py:237-243) or as .npy.
+With --output the embeddings are learned after the walks (learn_embeddings,
+main.py:92-101: skip-gram with negative sampling, --dimensions, --window-size,
+--iter, --negative, --sample) by the HIP trainer (gwamd.embed) and written in
+save_word2vec_format's text form; in scale mode the walks stay in HBM between
+the two steps.  --workers is accepted and unused (the trainer sizes its own
+concurrency).  Without --output only the walks are produced, as before.
+Walks are written in DeepSim's save_list format (DeepSim/src/main.py:237-243)
+or as .npy.
 
 --mode replay : reference-exact (networkx graph, global random/np.random
                 seeded with --seed, per-edge alias tables on the GPU);
@@ -37,7 +41,8 @@ import numpy as np
 def parse_args(argv=None, p=1.0, q=1.0):
     ap = argparse.ArgumentParser(description="Run node2vec walk generation on MI355X.")
     ap.add_argument("--input", nargs="?", default="../graph/karate.edgelist", help="Input graph path")
-    ap.add_argument("--output", nargs="?", default=None, help="(embeddings path; gensim step not run)")
+    ap.add_argument("--output", nargs="?", default=None, help="Embeddings path (word2vec text format); trained on the GPU after the walks, "
+                         "on rank 0 only when launched with several ranks.  Omitted: walks only")
     ap.add_argument("--walks", default="walks.txt", help="walks output (save_list format, or .npy)")
     ap.add_argument("--dimensions", type=int, default=128)
     ap.add_argument("--walk-length", type=int, default=80)
@@ -45,6 +50,8 @@ def parse_args(argv=None, p=1.0, q=1.0):
     ap.add_argument("--window-size", type=int, default=10)
     ap.add_argument("--iter", default=10, type=int)
     ap.add_argument("--workers", type=int, default=8)
+    ap.add_argument("--negative", type=int, default=5, help="negative samples per pair (with --output)")
+    ap.add_argument("--sample", type=float, default=1e-3, help="subsampling threshold, 0 disables (with --output)")
     ap.add_argument("--p", type=float, default=p)
     ap.add_argument("--q", type=float, default=q)
     ap.add_argument("--delimiter", type=str, default=",")
@@ -169,6 +176,10 @@ def _scale(args):
         dist.destroy_process_group()
         if rank != 0:
             return None
+    if args.output:
+        # rank 0 holds every walk here; a single-GPU run trains on the tensor the walk kernel wrote
+        Wd = W if W.is_cuda else W.to(f"cuda:{device}")
+        _embed(args, Wd.contiguous(), g.export_csr()["labels"], device)
     W, lens = W.cpu().numpy(), lens.cpu().numpy()
     if args.walks.endswith(".npy"):
         lab = g.export_csr()["labels"]
@@ -176,6 +187,15 @@ def _scale(args):
     else:
         io.save_walks(g, args.walks, W, lens)
     return nwalks
+
+
+def _embed(args, walks, labels, device):
+    """main.py:92-101 learn_embeddings on dense-id walks (-1 padded) + save_word2vec_format."""
+    from .embed import learn_embeddings
+    emb = learn_embeddings(walks, labels, dimensions=args.dimensions, window_size=args.window_size, iter=args.iter,
+                           negative=args.negative, sample=args.sample, seed=args.seed, device=device)
+    emb.save_word2vec_format(args.output)
+    print(f"{len(emb.index2word)} x {args.dimensions} embeddings -> {args.output}", file=sys.stderr)
 
 
 def main(argv=None):
@@ -198,6 +218,13 @@ def main(argv=None):
         else:
             io.save_list(walks, args.walks)
         nwalks = len(walks)
+        if args.output:
+            labels = np.array(sorted(nx_G.nodes()), np.int64)
+            dense = {int(l): i for i, l in enumerate(labels)}
+            W = np.full((len(walks), args.walk_length), -1, np.int32)
+            for i, w in enumerate(walks):
+                W[i, :len(w)] = [dense[int(v)] for v in w]
+            _embed(args, W, labels, args.device)
     else:
         nwalks = _scale(args)
         if nwalks is None:  # not rank 0

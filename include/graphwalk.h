@@ -460,6 +460,115 @@ int gw_write_sim_text_cachemap(const char* path, const int32_t* keys,
                                const int32_t* row_ids, int64_t nrows,
                                int capacity, int topk, const char* sep);
 
+/* ---- embeddings: skip-gram with negative sampling ---------------------------- */
+/* Replaces learn_embeddings (node2vec/src/main.py:92-101; DeepSim/src/
+ * main.py:215-216): Word2Vec(walks, size, window, min_count=0, sg=1, iter)
+ * and save_word2vec_format, trained on the walk matrix gw_n2v_walks writes
+ * (int32 dense ids, -1 padded; a walk ends at its first -1).  The law is
+ * gensim's sg=1, hs=0, negative=K training made counter-based
+ * (csrc/gw_sgns_law.h holds the one definition host and kernel share):
+ *   vocabulary  cnt[v] = occurrences of v, every vertex that occurs is kept;
+ *   subsampling keep probability min(1, (sqrt(cnt/(sample*T)) + 1) *
+ *               (sample*T)/cnt), T = sum cnt (sample = 0: keep all), computed
+ *               in fp64 on the host and stored as floor(p * 2^32)
+ *               (0xFFFFFFFF = always); a token is kept iff its word < it;
+ *   negatives   P(v) ~ cnt[v]^0.75 (fp64 on the host), Vose alias table with
+ *               q stored as floor(q * 2^32); a draw from Philox words (x, y)
+ *               is k = (x * n) >> 32, t = y < thr[k] ? k : J[k]; a negative
+ *               equal to the centre word is skipped;
+ *   windows     per kept token i of a walk's kept sequence s: b = y % window;
+ *               for j in [i-window+b, i+window-b], j != i, ascending: the pair
+ *               (input row syn0[s[j]]; target s[i] with label 1, then the K
+ *               negatives with label 0);
+ *   target      f = dot(l1, syn1neg[t]); |f| >= 6 skips it; else g = (label -
+ *               expTable[int((f+6)*(1000/12))]) * alpha; neu1e += g*syn1neg[t];
+ *               syn1neg[t] += g*l1; after a pair's targets syn0[s[j]] += neu1e;
+ *   alpha(e,w)  alpha - (alpha - min_alpha) * (e*nwalks + w) / (epochs*nwalks)
+ *               in fp64, cast to fp32 (e = epoch, w = walk index);
+ *   initial     syn0[v][d] = (u - 0.5) / dim, syn1neg = 0.
+ * Philox4x32-10 keying (k0 = seed low, k1 = seed high ^ tag; never the launch
+ * geometry), w = global walk index, pos = position in the walk as given:
+ *   token    tag "sgT0": counter (w low, w high, pos, epoch) -> x: subsampling
+ *            word, y: window word;
+ *   negative tag "sgN0": counter (w low, w high, centre pos, epoch << 20 |
+ *            slot << 9 | k), slot = j - (i - window) in [0, 2*window], k the
+ *            negative's index in [0, K) -> (x, y) of the alias draw;
+ *   initial  tag "sgI0": counter (v, 0, d, 0) -> x, u = x * 2^-32.
+ * Hence window <= 1023, negative <= 511, epochs <= 4096, walk_len <= 2^20
+ * (the kernel: walk_len <= 2048, its kept sequence lives in LDS).
+ * Sequential order: epochs, walks, positions, pairs, targets ascending; a
+ * dot product sums 64 lane-strided partials (16 B chunks) and then a fixed
+ * butterfly; the host evaluation (device = -1) runs the same order, so it
+ * equals the kernel at concurrency = 1 bit for bit (tested).               */
+typedef struct gw_sgns gw_sgns;
+typedef struct gw_sgns_params_t {
+  int32_t struct_size; /* sizeof(gw_sgns_params_t) as the caller compiled it:
+                          min(struct_size, the library's size) bytes are read,
+                          the rest keeps the defaults below                    */
+  int32_t dim;         /* 1..1024 (default 128)                                 */
+  int32_t window;      /* 1..1023 (5)                                           */
+  int32_t negative;    /* 0..511 (5)                                            */
+  int32_t epochs;      /* 1..4096: the schedule's length (5)                    */
+  int32_t reserved0;   /* 0                                                     */
+  double alpha;        /* 0.025                                                 */
+  double min_alpha;    /* 0.0001                                                */
+  double sample;       /* 1e-3; 0 disables subsampling                          */
+  uint64_t seed;       /* 0                                                     */
+} gw_sgns_params_t;
+typedef struct gw_sgns_stats_t {
+  int64_t tokens_kept;      /* tokens that survived subsampling                */
+  int64_t pairs;            /* (input, centre) pairs trained                   */
+  int64_t negatives;        /* negatives drawn (K per pair)                    */
+  int64_t negatives_centre; /* of those, skipped as equal to the centre word   */
+  int64_t targets_clipped;  /* targets skipped at |f| >= 6                     */
+} gw_sgns_stats_t;
+/* device >= 0: a GPU; device = -1: host evaluation of the same law (no GPU
+ * needed; walks are then host pointers).  params NULL = the defaults.  n =
+ * vertices (ids in [0, n)).                                                 */
+int gw_sgns_create(int device, int64_t n, const gw_sgns_params_t* params, gw_sgns** out);
+int gw_sgns_free(gw_sgns* m);
+/* message of the last failing call on this handle (NULL: the last failing
+ * handle-less call on this thread, as gw_last_error(NULL))                   */
+const char* gw_sgns_last_error(const gw_sgns* m);
+/* Counts, keep thresholds, alias sampler, exp table and the initial syn0 /
+ * syn1neg (the histogram and the initialisation run on the device).  An id
+ * outside [0, n) (other than the -1 padding) gives GW_ERR_RANGE.
+ * Synchronous.                                                               */
+int gw_sgns_build_vocab(gw_sgns* m, const int32_t* walks, int64_t nwalks, int walk_len);
+/* Epochs [epoch_begin, epoch_begin + epoch_count) of params.epochs over the
+ * corpus (the one build_vocab counted).  `concurrency` waves train at once,
+ * Hogwild like gensim's workers: wave c takes walks c, c + concurrency, ...
+ * of each epoch; 1 is exactly the sequential law.  0 = auto:
+ * min(nwalks, 16 * compute units, max(1, n / 32)) - never more than one wave
+ * per 32 vertices, so that rows are rarely trained by two waves at once.
+ * Rows are loaded and stored with 16 B agent-scope (sc1) accesses, so a wave
+ * never trains against a copy older than the L2 / memory holds.  The draws
+ * do not depend on concurrency.  stats (optional) += this call's counts.
+ * Runs on `stream` and synchronises it.  GW_ERR_STATE before build_vocab.    */
+int gw_sgns_train(gw_sgns* m, const int32_t* walks, int64_t nwalks, int walk_len, int epoch_begin,
+                  int epoch_count, int concurrency, gw_sgns_stats_t* stats, void* stream);
+/* Host copies: syn0[n*dim], syn1neg[n*dim] (dense rows), counts[n]; NULL skips */
+int gw_sgns_export(gw_sgns* m, float* syn0, float* syn1neg, int64_t* counts);
+/* The negative sampler and the keep thresholds: J[n], thr[n], keep_thr[n]   */
+int gw_sgns_sampler_export(const gw_sgns* m, int32_t* J, uint32_t* thr, uint32_t* keep_thr);
+/* syn0 where it lives (HBM of the handle's device, or host memory at device
+ * = -1): row v at ptr + v * pitch floats, dim used (zero-copy for torch)     */
+int gw_sgns_vectors_dev(gw_sgns* m, float** ptr, int64_t* pitch);
+/* concurrency an auto (0) gw_sgns_train call over nwalks walks uses          */
+int gw_sgns_auto_concurrency_for(const gw_sgns* m, int64_t nwalks, int32_t* concurrency);
+/* Registers per lane, scratch bytes per lane (expected 0) and LDS bytes per
+ * workgroup of the training kernel this handle launches for walk_len
+ * (hipFuncGetAttributes).                                                    */
+int gw_sgns_kernel_attrs(gw_sgns* m, int walk_len, int32_t* vgprs, int32_t* scratch_bytes, int32_t* lds_bytes);
+/* save_word2vec_format(path) (main.py:99): "<V'> <dim>\n", V' = vertices with
+ * counts > 0, then one row per such vertex "<label> v v ... v\n" (%f, single
+ * spaces), by count descending, ties by label ascending (gensim's own tie
+ * order follows its vocabulary dict's iteration order, which is arbitrary
+ * under the Python the reference ran on).  syn0[n*dim] host rows, labels NULL
+ * = dense ids.                                                               */
+int gw_write_word2vec_text(const char* path, const float* syn0, const int64_t* counts, const int64_t* labels,
+                           int64_t n, int dim);
+
 /* ---- multi-GPU exchange (RCCL over xGMI) ---------------------------------- */
 /* the graph is replicated and units (walks, TopSim sources) are
  * sharded by global index with no data-path collective; the only exchange is

@@ -1,7 +1,7 @@
 #!/bin/bash
 # ASan + UBSan run of the host code: the edge-list parsers, graph
 # builders, writers and C-ABI argument checks (gw_graph_host.cpp, gw_capi.cpp,
-# gw_comm.cpp) and the oracle (oracle.c) compiled with
+# gw_comm.cpp, gw_sgns_host.cpp) and the oracle (oracle.c) compiled with
 # -fsanitize=address,undefined, linked with the unchanged HIP objects (device
 # code is not sanitized: GPU ASan is not available on this pool), then the CPU
 # test suite (pytest -m "not gpu") under the sanitizer runtimes.
@@ -12,13 +12,13 @@ python graph-embedding_amd/build.py > /dev/null
 B=graph-embedding_amd/build_san
 mkdir -p $B
 SAN="-O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined"
-for f in gw_graph_host gw_capi gw_comm; do
+for f in gw_graph_host gw_capi gw_comm gw_sgns_host; do
   g++ $SAN -std=c++17 -fPIC -fopenmp -ffp-contract=off -Wall -Wno-unused-function -Iinclude -I/opt/rocm/include \
       -D__HIP_PLATFORM_AMD__ -c graph-embedding_amd/csrc/$f.cpp -o $B/$f.o &
 done
 gcc $SAN -fPIC -fopenmp -ffp-contract=off -std=gnu11 -shared -o $B/liboracle_san.so oracle/oracle.c -lm &
 wait
-g++ -shared -fsanitize=address,undefined -o $B/libgraphwalk_san.so $B/gw_graph_host.o $B/gw_capi.o $B/gw_comm.o \
+g++ -shared -fsanitize=address,undefined -o $B/libgraphwalk_san.so $B/gw_graph_host.o $B/gw_capi.o $B/gw_comm.o $B/gw_sgns_host.o \
     graph-embedding_amd/build/*.hip.o -L/opt/rocm/lib -lamdhip64 -fopenmp -ldl -Wl,-rpath,/opt/rocm/lib
 ASAN_RT=$(gcc -print-file-name=libasan.so)
 UBSAN_RT=$(gcc -print-file-name=libubsan.so)
