@@ -7,6 +7,9 @@ Host-side mirror of the reference interfaces over the libgraphwalk C ABI
 * `gwamd.embed`     — learn_embeddings (node2vec/src/main.py:92-101): skip-gram /
                       negative-sampling training on the device-resident walks,
                       save_word2vec_format
+* `gwamd.deepsim`   — DeepSim/src/DeepSim.py (main, save_embeddings): the SimRank-guided
+                      net trained on the device-resident walks and SimRank rows;
+                      `python -m gwamd.deepsim` takes DeepSim/src/main.py's flags
 * `gwamd.topsim`    — DeepSim/TopSimAll structures.Graph, TopSim_singleSample,
                       TopSim_Enumerate, SingleRandomWalk, SimRank (naive),
                       Print.printByOrder/printByOrderAll,

@@ -104,6 +104,24 @@ class SgnsStats(ctypes.Structure):
         return tuple(getattr(self, f) for f, _ in self._fields_)
 
 
+DEEPSIM_FALLBACK_ROW_MIN = 0
+DEEPSIM_FALLBACK_POSITION = 1
+
+
+class DeepSimParams(ctypes.Structure):
+    """gw_deepsim_params_t (include/graphwalk.h); struct_size is filled in by default."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("dim", ctypes.c_int32), ("window", ctypes.c_int32),
+                ("batch", ctypes.c_int32), ("fallback", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+                ("vertex_num", ctypes.c_int64), ("learning_rate", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("epsilon", ctypes.c_double), ("score_scale", ctypes.c_double),
+                ("seed", ctypes.c_uint64)]
+
+    def __init__(self, vertex_num=0, dim=128, window=10, batch=128, fallback=DEEPSIM_FALLBACK_ROW_MIN,
+                 learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8, score_scale=1.0, seed=0):
+        super().__init__(ctypes.sizeof(DeepSimParams), dim, window, batch, fallback, 0, vertex_num, learning_rate,
+                         beta1, beta2, epsilon, score_scale, seed)
+
+
 P = ctypes.c_void_p
 I32 = ctypes.c_int32
 I64 = ctypes.c_int64
@@ -183,6 +201,18 @@ SIGNATURES = {
     "gw_sgns_auto_concurrency_for": (ctypes.c_int, [P, I64, PI32]),
     "gw_sgns_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, PI32, PI32, PI32]),
     "gw_write_word2vec_text": (ctypes.c_int, [CP, P, P, P, I64, ctypes.c_int]),
+    "gw_deepsim_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(DeepSimParams), PP]),
+    "gw_deepsim_free": (ctypes.c_int, [P]),
+    "gw_deepsim_last_error": (CP, [P]),
+    "gw_deepsim_set_simrank": (ctypes.c_int, [P, P, P, ctypes.c_int]),
+    "gw_deepsim_set_walks": (ctypes.c_int, [P, P, I64, ctypes.c_int, P, I64]),
+    "gw_deepsim_train": (ctypes.c_int, [P, I64, I64, P, P]),
+    "gw_deepsim_gradients": (ctypes.c_int, [P, I64, P, P, P, P]),
+    "gw_deepsim_batch": (ctypes.c_int, [P, I64, P, P, P, P, P]),
+    "gw_deepsim_export": (ctypes.c_int, [P, PP, PP, PP]),
+    "gw_deepsim_vectors_dev": (ctypes.c_int, [P, PP, PI64]),
+    "gw_deepsim_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
+    "gw_write_deepsim_text": (ctypes.c_int, [CP, P, I64, ctypes.c_int]),
     "gw_comm_unique_id": (ctypes.c_int, [P]),
     "gw_comm_init": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, PP]),
     "gw_comm_allgather": (ctypes.c_int, [P, P, P, I64, ctypes.c_int, P]),
@@ -210,12 +240,17 @@ def lib():
     return _lib
 
 
-def check(rc, handle=None, sgns=None):
-    """Raise for a failing status; `handle` a gw_graph, `sgns` a gw_sgns (for the message)."""
+def check(rc, handle=None, sgns=None, deepsim=None):
+    """Raise for a failing status; `handle` a gw_graph, `sgns` a gw_sgns, `deepsim` a gw_deepsim or True for a
+    handle-less gw_deepsim call (for the message)."""
     if rc == GW_OK:
         return
     L = lib()
-    msg = (L.gw_sgns_last_error(sgns) if sgns is not None else L.gw_last_error(handle)).decode(errors="replace")
+    if deepsim is not None:
+        msg = L.gw_deepsim_last_error(None if deepsim is True else deepsim)
+    else:
+        msg = L.gw_sgns_last_error(sgns) if sgns is not None else L.gw_last_error(handle)
+    msg = msg.decode(errors="replace")
     if rc == GW_ERR_INVALID:
         raise ValueError(msg)
     if rc == GW_ERR_IO:

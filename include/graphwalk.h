@@ -569,6 +569,97 @@ int gw_sgns_kernel_attrs(gw_sgns* m, int walk_len, int32_t* vgprs, int32_t* scra
 int gw_write_word2vec_text(const char* path, const float* syn0, const int64_t* counts, const int64_t* labels,
                            int64_t n, int dim);
 
+/* ---- embeddings: DeepSim (SimRank-guided one-hidden-layer net) --------------- */
+/* Replaces DeepSim.main (DeepSim/src/DeepSim.py:386-422): per step a batch of
+ * `batch` distinct walks, one centre position each, targets y[j] = sim(c, j)
+ * for the distinct vertices j of the centre's window (2*window+1 tokens);
+ *   hidden = relu(w1[c] + b1), logits = hidden . w2 + b2,
+ *   loss = mean_b( -sum_j y[b][j] * log softmax(logits[b])[j] ),
+ * TF1 Adam (lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), t = step + 1) dense
+ * over w1 [V][dim], b1 [dim], w2 [dim][V], b2 [V]; the embedding is w1.
+ * csrc/gw_deepsim_law.h holds the one definition (draws, float order) that
+ * the kernels and the host evaluation (device = -1) share; they agree bit for
+ * bit (tested).  Everything is in vertex-index space [0, V): the row numbers
+ * of the .sim.txt.  Philox4x32-10 keying (k0 = seed low, k1 = seed high ^ tag):
+ *   walk     tag "dsP0": slot s of step t takes eligible[gw_feistel_perm(s,
+ *            n_eligible, k0 ^ t high, k1, tweak = t low)];
+ *   position tag "dsB0": counter (t low, t high, s, 0) -> x,
+ *            pos = window + ((x * (len - 2*window)) >> 32);
+ *   initial  tag "dsI0": counter (index low, index high, tensor, attempt),
+ *            tensor 0 = w1, 2 = w2; Box-Muller in fp64 on u1 = (x+1) * 2^-32,
+ *            u2 = y * 2^-32, redrawn (attempt + 1) while |z| > 2; 0.1 * z.
+ * Device path: dim and batch multiples of 32 in [32, 128], window <= 64,
+ * topk <= 1024 (else GW_ERR_UNSUPPORTED); the host path takes any positive
+ * values.  HBM: 24 * V * dim + 12 * (V + dim) bytes of parameters and Adam
+ * state, 4 * V * dim for the w1 gradient rows, 4 * batch * V logits,
+ * 4 * ceil(V / 64) * batch * (dim + 2) of per-tile partials and the table's
+ * 8 * V * topk.                                                               */
+#define GW_DEEPSIM_FALLBACK_ROW_MIN 0  /* absent id: tem[centre] (get_input_output :242-245) */
+#define GW_DEEPSIM_FALLBACK_POSITION 1 /* absent id: tem[pos] (get_batch :319 read literally) */
+typedef struct gw_deepsim gw_deepsim;
+typedef struct gw_deepsim_params_t {
+  int32_t struct_size;  /* as gw_sgns_params_t.struct_size                        */
+  int32_t dim;          /* 128                                                    */
+  int32_t window;       /* 10                                                     */
+  int32_t batch;        /* 128                                                    */
+  int32_t fallback;     /* GW_DEEPSIM_FALLBACK_ROW_MIN                            */
+  int32_t reserved0;    /* 0                                                      */
+  int64_t vertex_num;   /* V (required)                                           */
+  double learning_rate; /* 0.001                                                  */
+  double beta1;         /* 0.9                                                    */
+  double beta2;         /* 0.999                                                  */
+  double epsilon;       /* 1e-8                                                   */
+  double score_scale;   /* 1.0; 1 / SAMPLE turns gw_topsim scores into SimRank    */
+  uint64_t seed;        /* 0                                                      */
+} gw_deepsim_params_t;
+/* device >= 0: a GPU; -1: the host evaluation.  Initialises w1, w2 (biases and
+ * Adam state 0).                                                               */
+int gw_deepsim_create(int device, const gw_deepsim_params_t* params, gw_deepsim** out);
+int gw_deepsim_free(gw_deepsim* m);
+const char* gw_deepsim_last_error(const gw_deepsim* m);
+/* The SimRank table: ids[V][topk] (-1 padded) and fp64 scores[V][topk] in the
+ * order gw_topsim / the .sim.txt give them (score descending); device pointers
+ * for device >= 0, host pointers for device = -1.  Scores are multiplied by
+ * score_scale, entries <= 1e-8 are dropped, tem[v] = the last kept value in
+ * that order (0 for an empty row), rows are then sorted by id, values stored
+ * as fp32.  The build itself runs on the host (one copy each way).  An id
+ * outside [-1, V) gives GW_ERR_RANGE.  Synchronous.                           */
+int gw_deepsim_set_simrank(gw_deepsim* m, const int32_t* ids, const double* scores, int topk);
+/* The walk matrix [nwalks][walk_len] (int32, -1 padded; device memory for
+ * device >= 0) stays where it is and must outlive the training calls; only
+ * the list of eligible walks (len >= 2*window+1) is built.  labels (host,
+ * [n_labels] or NULL = identity) maps a token to its vertex index; a token
+ * outside [0, n_labels) or a mapped one outside [0, V) gives GW_ERR_RANGE.
+ * Fewer eligible walks than `batch` gives GW_ERR_INVALID.  Synchronous.       */
+int gw_deepsim_set_walks(gw_deepsim* m, const int32_t* walks, int64_t nwalks, int walk_len, const int64_t* labels,
+                         int64_t n_labels);
+/* Steps [step_begin, step_begin + step_count); pieces equal one call.
+ * loss_out[step_count] (host, optional): each step's loss before its update.
+ * Runs on `stream` and synchronises it.                                       */
+int gw_deepsim_train(gw_deepsim* m, int64_t step_begin, int64_t step_count, double* loss_out, void* stream);
+/* Gradient of step's batch at the current parameters (host copies, NULL
+ * skips): gw1[V*dim], gb1[dim], gw2[dim*V], gb2[V].  Nothing is updated.      */
+int gw_deepsim_gradients(gw_deepsim* m, int64_t step, float* gw1, float* gb1, float* gw2, float* gb2);
+/* Host copies of step's batch: centre[batch], tgt_id / tgt_val
+ * [batch][2*window+1] (the first tgt_n[b] of a row are used, the rest -1 / 0),
+ * tgt_n[batch], ysum[batch].  NULL skips.                                     */
+int gw_deepsim_batch(gw_deepsim* m, int64_t step, int32_t* centre, int32_t* tgt_id, float* tgt_val, int32_t* tgt_n,
+                     float* ysum);
+/* Host copies, reference shapes (NULL skips): par / adam_m / adam_v each
+ * {w1[V*dim], b1[dim], w2[dim*V], b2[V]}.                                     */
+int gw_deepsim_export(gw_deepsim* m, float* const par[4], float* const adam_m[4], float* const adam_v[4]);
+/* w1 where it lives: row v at ptr + v * pitch floats                          */
+int gw_deepsim_vectors_dev(gw_deepsim* m, float** ptr, int64_t* pitch);
+/* Per kernel of the step chain (up to `cap`): name, registers per lane,
+ * scratch bytes per lane, LDS bytes per workgroup; *count = kernels.          */
+int gw_deepsim_kernel_attrs(gw_deepsim* m, int cap, const char** names, int32_t* vgprs, int32_t* scratch_bytes,
+                            int32_t* lds_bytes, int32_t* count);
+/* save_embeddings (DeepSim.py:344-362): "<n> <dim>\n" (the reference writes
+ * the literal 128), then "<i> v v ... v\n" per row, each value as
+ * str(numpy.float32) prints it (shortest round-trip digits; positional for
+ * 1e-4 <= |x| < 1e16, else scientific with a two-digit exponent).             */
+int gw_write_deepsim_text(const char* path, const float* w1, int64_t n, int dim);
+
 /* ---- multi-GPU exchange (RCCL over xGMI) ---------------------------------- */
 /* the graph is replicated and units (walks, TopSim sources) are
  * sharded by global index with no data-path collective; the only exchange is
