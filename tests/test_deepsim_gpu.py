@@ -61,6 +61,11 @@ PARITY = [
     (3 * TW + 5, 128, 128, 5, 23, 0, False),
     (3 * TW + 5, 128, 128, 1, 7, 1, True),
     (34, 32, 32, 5, 23, 1, True),
+    # the MFMA block maps (block q = wave + 4u against nblk) where B / 32 and d / 32 differ or are odd
+    (3 * TW + 5, 96, 32, 2, 11, 0, False),
+    (3 * TW + 5, 96, 64, 2, 11, 1, True),
+    (3 * TW + 5, 32, 128, 2, 11, 0, True),
+    (3 * TW + 5, 128, 32, 2, 11, 1, False),
 ]
 
 
@@ -82,7 +87,104 @@ def test_kernel_equals_host_bitwise(V, B, d, k, L, fallback, labelled):
     assert_batch_equal(dev, host, 19)
 
 
-@pytest.mark.parametrize("V,B,d,k", [(34, 32, 32, 2), (3 * TW + 5, 64, 96, 5)])
+def check_steps(dev, host, marks):
+    """Batch 0, then state, Adam moments and losses after each count of steps in `marks`, then the last batch."""
+    b0 = assert_batch_equal(dev, host, 0)
+    done = 0
+    for upto in marks:
+        ld, lh = dev.train(done, upto - done), host.train(done, upto - done)
+        done = upto
+        assert_state_equal(dev, host)
+        assert np.all(np.isfinite(lh)) and np.all(np.abs(ld - lh) <= 1e-5 * np.abs(lh))
+    assert_batch_equal(dev, host, done - 1)
+    return b0
+
+
+# k_ds_rowstats walks the tile partials in runs of 16 tiles, 8 runs per outer trip: 17 tiles hand S from run 0 to
+# run 1, 128 tiles fill one trip exactly, 129 start the second, 162 is blog's V.  k_ds_reduce_dh and the part /
+# tmax / tsum strides see the same tile counts.
+@pytest.mark.parametrize("V,B,d,marks", [(1025, 32, 32, (1, 3, 20)), (8192, 64, 32, (1, 3)), (8193, 64, 64, (1, 3)),
+                                         (10313, 128, 128, (1, 3))])
+def test_many_tiles(V, B, d, marks):
+    assert (V + TW - 1) // TW in (17, 128, 129, 162)
+    dev, host = pair(V, B, d, 2, 11, 0, V != 8192)
+    check_steps(dev, host, marks)
+    dev.free()
+    host.free()
+
+
+@pytest.mark.parametrize("fallback", [0, 1])
+@pytest.mark.parametrize("k", [32, 33, 64])
+def test_wide_windows(k, fallback):
+    """W = 2k+1 in {65, 67, 129}: the 64-lane loops of k_ds_batch take a second and a third trip."""
+    dev, host = pair(200, 32, 32, k, 140, fallback, fallback == 1)
+    b0 = check_steps(dev, host, (1, 3))
+    print(f"k {k}: max tgt_n {b0['tgt_n'].max()}")
+    if k == 64:
+        assert b0["tgt_n"].max() > 64   # more distinct targets than lanes
+    else:
+        assert b0["tgt_n"].max() > 32
+
+
+def test_deep_table():
+    """topk = 1024 (GW_DS_MAX_TOPK) with rows that are full: ten rounds of the binary search.  The walks pass
+    through the full rows' vertices, so those rows are looked up as centres; found values come from the row, the
+    rest are the row's smallest."""
+    from gwamd import _lib as Cl
+    from gwamd import deepsim
+    V, topk, full, scale = 1100, 1024, 24, 0.5
+    rng = np.random.RandomState(13)
+    ids = np.full((V, topk), -1, np.int32)
+    sc = np.zeros((V, topk), np.float64)
+    for v in range(V):
+        n = topk if v < full else int(rng.randint(1, 8))
+        ids[v, :n] = rng.choice(V, n, replace=False)
+        sc[v, :n] = np.sort(rng.uniform(0.01, 0.9, n))[::-1]
+    W = rng.randint(0, V, (80, 11)).astype(np.int32)
+    W[:, ::2] = rng.randint(0, full, W[:, ::2].shape)
+    kw = dict(dim=32, window=2, batch=32, seed=7, score_scale=scale)
+    dev, host = trainer(V, ids, sc, W, device=0, **kw), trainer(V, ids, sc, W, device=-1, **kw)
+    hits = misses = 0
+    for step in (0, 3):
+        b = assert_batch_equal(dev, host, step)
+        for s in range(32):
+            c = int(b["centre"][s])
+            if c >= full:
+                continue
+            row = {int(i): np.float32(x * scale) for i, x in zip(ids[c], sc[c])}
+            for q in range(b["tgt_n"][s]):
+                j = int(b["tgt_id"][s, q])
+                assert b["tgt_val"][s, q] == row.get(j, np.float32(sc[c, -1] * scale))
+                hits += j in row
+                misses += j not in row
+    assert hits > 32 and misses > 0
+    dev.train(0, 2)
+    host.train(0, 2)
+    assert_state_equal(dev, host)
+    wide = deepsim.DeepSim(V, device=0, **kw)
+    with pytest.raises(Cl.UnsupportedError, match="kernels take"):
+        wide.set_simrank(np.full((V, topk + 1), -1, np.int32), np.zeros((V, topk + 1)))
+    deepsim.DeepSim(V, device=-1, **kw).set_simrank(np.full((V, topk + 1), -1, np.int32), np.zeros((V, topk + 1)))
+
+
+def test_label_map_longer_than_the_vertex_count():
+    """Tokens in [0, 2V) through a map of 2V entries into [0, V): tokens t and t + V are the same vertex, so the
+    batches equal those of the unshifted walks under the map's first half."""
+    V, B, d, k = 3 * TW + 5, 32, 32, 2
+    ids, sc, W = corpus(V, k, 11, B + 40, 7)
+    rng = np.random.RandomState(5)
+    perm = rng.permutation(V).astype(np.int64)
+    labels = np.concatenate([perm, perm])
+    W2 = np.where(W >= 0, W + V * rng.randint(0, 2, W.shape), -1).astype(np.int32)
+    assert W2.max() >= V and (W2 < V).any()
+    kw = dict(dim=d, window=k, batch=B, seed=7, score_scale=0.5)
+    dev, host = trainer(V, ids, sc, W2, labels, device=0, **kw), trainer(V, ids, sc, W2, labels, device=-1, **kw)
+    check_steps(dev, host, (1, 3))
+    assert_batch_equal(host, trainer(V, ids, sc, W, perm, device=-1, **kw), 2)
+    assert_state_equal(dev, host)
+
+
+@pytest.mark.parametrize("V,B,d,k", [(34, 32, 32, 2), (3 * TW + 5, 64, 96, 5), (8193, 64, 64, 2)])
 def test_gradients_equal_host_bitwise(V, B, d, k):
     dev, host = pair(V, B, d, k, 4 * k + 3, 0, False, seed=3)
     for step in (0, 5):

@@ -69,14 +69,32 @@ def barbell_corpus():
     return W, 12
 
 
+def uniform_corpus(n, nwalks, width, seed, lens=None):
+    """`nwalks` rows of uniform ids in [0, n) (fixed seed); row w is cut to lens[w] tokens by -1."""
+    W = np.random.RandomState(seed).randint(0, n, (nwalks, width)).astype(np.int32)
+    for w, ln in enumerate(lens or ()):
+        W[w, ln:] = -1
+    return W, n
+
+
+# walk lengths around the kernel's 64-position trips, the reference's default 80 and the full width
+LONG_LENS = (130, 0, 1, 63, 64, 65, 80, 128, 130, 97)
+
+
+def long_walk_corpus(width=130):
+    """40 vertices, 10 walks of `width` with the lengths LONG_LENS (capped at the width)."""
+    return uniform_corpus(40, len(LONG_LENS), width, 77, [min(x, width) for x in LONG_LENS])
+
+
 # (dim, window, K, epochs, sample); the GPU parity test reuses them
 CASES = [(8, 3, 2, 2, 0.0), (100, 1, 5, 1, 0.01), (8, 3, 0, 1, 0.0)]
 
 
-def train_lib(W, n, dim, window, K, epochs, sample, seed=5, device=-1, concurrency=1):
-    """Train with the library; returns (syn0, syn1neg, stats tuple, sampler tables, counts)."""
+def train_lib(W, n, dim, window, K, epochs, sample, seed=5, device=-1, concurrency=1, **extra):
+    """Train with the library; returns (syn0, syn1neg, stats tuple, sampler tables, counts).  `extra`: further
+    gw_sgns_params_t fields (alpha, min_alpha)."""
     from gwamd.embed import SGNS
-    m = SGNS(n, device=device, dim=dim, window=window, negative=K, epochs=epochs, sample=sample, seed=seed)
+    m = SGNS(n, device=device, dim=dim, window=window, negative=K, epochs=epochs, sample=sample, seed=seed, **extra)
     if device >= 0:
         import torch
         Wd = torch.as_tensor(W, device=f"cuda:{device}")
@@ -191,10 +209,8 @@ def test_vocabulary_and_sampler():
     assert np.abs(keep_thr.astype(np.float64) - want).max() <= 1.0
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "dim%d_w%d_K%d_e%d_s%g" % c)
-def test_host_law_matches_restatement(case):
+def check_restatement(W, n, case):
     dim, window, K, epochs, sample = case
-    W, n = barbell_corpus()
     syn0, syn1, st, tables, _ = train_lib(W, n, dim, window, K, epochs, sample)
     r64 = restate(W, n, dim, window, K, epochs, sample, 5, tables, np.float64)
     r32 = restate(W, n, dim, window, K, epochs, sample, 5, tables, np.float32)
@@ -217,6 +233,32 @@ def test_host_law_matches_restatement(case):
     assert dev32 > 0
     assert devlib <= 4 * dev32
     assert np.abs(syn1).max() > 0 and np.abs(syn0 - r64[0]).max() < np.abs(syn0).max()
+    return st
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "dim%d_w%d_K%d_e%d_s%g" % c)
+def test_host_law_matches_restatement(case):
+    check_restatement(*barbell_corpus(), case)
+
+
+# The shapes at which the kernel is compared with the host law beyond its first loop trips (test_sgns_gpu.py):
+# rows of more than one 16 B chunk per lane (dim 300: 75 chunks, lanes 0..10 hold two; dim 1024: four on every
+# lane), walks longer than 64 positions with subsampling on, and more than 64 negatives per pair.  Measured
+# deviation from the fp64 restatement (plain-order fp32 / library):
+#   barbell dim 300, window 2, K 2:             1.987e-07 / 1.987e-07
+#   barbell dim 1024, window 2, K 2:            5.518e-08 / 5.518e-08
+#   long walks dim 8, window 3, K 2, s 0.004:   2.255e-08 / 2.255e-08
+#   4 x 30 over 12 vertices, window 2, K 66:    6.224e-06 / 6.224e-06
+SHAPE_CASES = [("barbell", (300, 2, 2, 1, 0.0)), ("barbell", (1024, 2, 2, 1, 0.0)), ("long", (8, 3, 2, 1, 0.004)),
+               ("k66", (8, 2, 66, 1, 0.0))]
+
+
+@pytest.mark.parametrize("name,case", SHAPE_CASES, ids=lambda x: x if isinstance(x, str) else "dim%d_w%d_K%d_e%d_s%g" % x)
+def test_host_law_matches_restatement_at_kernel_shapes(name, case):
+    W, n = {"barbell": barbell_corpus, "long": long_walk_corpus, "k66": lambda: uniform_corpus(12, 4, 30, 21)}[name]()
+    st = check_restatement(W, n, case)
+    if name == "k66":
+        assert st[3] > 0   # negatives equal to the centre were drawn and skipped
 
 
 def test_word2vec_writer(tmp_path):
