@@ -149,7 +149,8 @@ struct gw_ts_sparse {
 };
 
 struct gw_graph {
-  gw_options_t opt{0, 0, -1, 0, 0, 0, 0};  // per-handle tuning (gw_graph_set_options)
+  // per-handle tuning (gw_graph_set_options); listed = -1, simrank_window = 0 (automatic)
+  gw_options_t opt{0, 0, -1, 0, 0, 0, /*simrank_window=*/0};
   // host CSR
   int semantics = 0;
   int directed = 0;

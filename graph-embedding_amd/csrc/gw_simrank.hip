@@ -350,7 +350,9 @@ int gw_dev_simrank_naive(gw_graph* g, double C, int iters, double* sim_dev, void
     // the HBM-row variant (same bits; tests compare the two)
     const int64_t cap = SR_LDS_BYTES / (int64_t)sizeof(double);
     const bool lds_row = m + 1 + SR_MIN_WIN <= cap && !g->opt.simrank_hbm_row;
-    const int win = (int)std::min<int64_t>(m, lds_row ? cap - m - 1 : cap);
+    // the simrank_window option only shrinks the window (tests: multi-window passes at small m)
+    const int64_t win_auto = std::min<int64_t>(m, lds_row ? cap - m - 1 : cap);
+    const int win = (int)(g->opt.simrank_window > 0 ? std::min<int64_t>(win_auto, g->opt.simrank_window) : win_auto);
     for (int r = 0; r < iters; ++r) {  // while (r++ < STEP), SimRank.java:38
       const int last = r == iters - 1;
       hipError_t e = lds_row ? launch_pass<true, false>(A, X, g->sr_work, 0, win, s)

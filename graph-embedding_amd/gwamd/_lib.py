@@ -81,7 +81,7 @@ class Options(ctypes.Structure):
     _fields_ = [("table_budget_bytes", ctypes.c_int64), ("expected_steps", ctypes.c_int64),
                 ("listed", ctypes.c_int32), ("simrank_hbm_row", ctypes.c_int32),
                 ("host_chunk_bytes", ctypes.c_int64), ("topsim_part_shrink", ctypes.c_int32),
-                ("reserved0", ctypes.c_int32)]
+                ("simrank_window", ctypes.c_int32)]
 
 
 class SgnsParams(ctypes.Structure):

@@ -110,7 +110,9 @@ class GWGraph:
     def options(self, **kw):
         """Read, and with keyword arguments update, the handle's gw_options_t
         (table_budget_bytes, expected_steps, listed, simrank_hbm_row,
-        host_chunk_bytes).  Returns the options in effect as a dict."""
+        host_chunk_bytes, topsim_part_shrink, simrank_window: rows per output
+        window of gw_simrank_naive, 0 = automatic, larger values are clamped).
+        Returns the options in effect as a dict."""
         o = C.Options()
         C.check(C.lib().gw_graph_get_options(self._h, ctypes.byref(o)), self._h)
         for k, v in kw.items():

@@ -397,7 +397,9 @@ class SimRank:
 
     def sim(self, v, w):
         """SimRank.java:67-77: one round for the pair (v, w) from the current
-        matrix (the identity before compute(); host arithmetic, O(deg^2))."""
+        matrix (the identity before compute()).  Host arithmetic: the double
+        loop's sum taken over the neighbour counts of v and w, O(V^2) whatever
+        the multiplicities (fp64 reassociation of the Java order)."""
         if v == w:
             return 1.0
         g = self.g
@@ -405,11 +407,11 @@ class SimRank:
         if dv == 0 or dw == 0:
             return 0.0
         S = self._sim if self._sim is not None else np.eye(self.COUNT)
-        result = 0.0
-        for vn in g.neighbors(v):
-            for wn in g.neighbors(w):
-                result += float(S[vn, wn])
-        return self.C * result / (dv * dw)
+        cv = np.bincount(g.neighbors(v), minlength=self.COUNT).astype(np.float64)
+        cw = np.bincount(g.neighbors(w), minlength=self.COUNT).astype(np.float64)
+        result = float(cv @ S @ cw)  # sum over a in N(v), b in N(w) of S[a, b] (:72-75)
+        dd = (dv * dw + (1 << 31)) % (1 << 32) - (1 << 31)  # Java int product (:76): wraps to signed 32 bits
+        return self.C * result / dd
 
     def getResult(self):
         if self._sim is None:

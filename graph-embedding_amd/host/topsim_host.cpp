@@ -153,7 +153,8 @@ double SimRank::sim(int v, int w) const {
   for (int vn : g_.neighbors(v))
     for (int wn : g_.neighbors(w))
       result += sim_.empty() ? (vn == wn ? 1.0 : 0.0) : sim_[(size_t)vn * V + wn];
-  return conf::MyConfiguration::C * result / (dv * dw);
+  // Java int product (:76): wraps to a signed 32-bit value, multiplied unsigned here (no signed overflow)
+  return conf::MyConfiguration::C * result / (int32_t)((uint32_t)dv * (uint32_t)dw);
 }
 }  // namespace simrank
 

@@ -147,7 +147,12 @@ typedef struct gw_options_t {
    * fills makes the call re-run without the append path (same scores);
    * exists to test that fallback                                          */
   int32_t topsim_part_shrink;
-  int32_t reserved0;  /* 0 */
+  /* gw_simrank_naive: rows per output window of the gather kernel.  0 = as
+   * many as the LDS budget allows; a positive value is clamped to that
+   * automatic size; negative = GW_ERR_INVALID.  Scores do not depend on it
+   * beyond fp64 reassociation (a window's entries are re-sliced over the
+   * waves); exists so tests reach the multi-window passes on small graphs  */
+  int32_t simrank_window;
 } gw_options_t;
 
 typedef struct gw_topsim_stats_t {

@@ -1080,7 +1080,8 @@ void or_simrank_naive(int64_t n, const int64_t* off, const int32_t* nbrs, double
           double res = 0.0;
           for (int64_t a = off[i]; a < off[i + 1]; ++a)
             for (int64_t b = off[j]; b < off[j + 1]; ++b) res += sim[(int64_t)nbrs[a] * n + nbrs[b]];
-          v = C * res / (double)(di * dj); /* :76 */
+          /* :76 multiplies Java ints: the product wraps to a signed 32-bit value */
+          v = C * res / (double)(int32_t)((uint32_t)di * (uint32_t)dj);
         }
         tmp[i * n + j] = v;
         tmp[j * n + i] = v;
@@ -1109,7 +1110,7 @@ int64_t or_simrank_round_rows(int64_t n, const int64_t* off, const int32_t* nbrs
         double res = 0.0;
         for (int64_t a = off[i]; a < off[i + 1]; ++a)
           for (int64_t b = off[j]; b < off[j + 1]; ++b) res += S[(int64_t)nbrs[a] * n + nbrs[b]];
-        v = C * res / (double)(di * dj);
+        v = C * res / (double)(int32_t)((uint32_t)di * (uint32_t)dj); /* Java int wrap, as above */
         pairs += di * dj;
       }
       out[(i - rb) * n + j] = v;

@@ -70,7 +70,7 @@ def test_naive_simrank_global_row_path_bitwise(gw):
 
 def test_naive_simrank_blog_recurrence(gw):
     """blog (10,313 vertices, 668K entries): too large for the oracle, so check
-    the recurrence: S3 == one host round of SimRank.sim() over the GPU's S2
+    the recurrence: S3 == one host round of SimRank.java:67-77 over the GPU's S2
     (diag restored to 1) on sampled pairs, plus symmetry / range / isolated
     vertex 0."""
     g = _graph("blog")
@@ -114,6 +114,16 @@ def test_naive_simrank_edge_cases(gw, oracle, tmp_path):
     v, w = 0, 1
     nv, nw = g.neighbors(v), g.neighbors(w)
     assert sr.sim(v, w) == pytest.approx(0.6 * sum(S[a, b] for a in nv for b in nw) / (len(nv) * len(nw)))
+    # ... and divides by Java's int product: 46341 * 46341 wraps negative, which turns the negative sum positive.
+    # One more round of the long-double reference; the mirror reads the GPU's matrix (within 1e-12 of the
+    # reference's, nearly all of the sum of one sign) and adds a handful of fp64 roundings of its own
+    # (the reference lives in the edges module: conftest.py is not the place for it, and tests/ is on sys.path)
+    from test_simrank_edges_gpu import next_round, reference, wrap_graph
+    gw_ = wrap_graph("neg_loops", tmp_path)
+    sw = topsim.SimRank(gw_, step=1)
+    sw.compute()
+    exp = float(next_round(gw_._offs, gw_._nbrs, 0.6, reference(gw_._offs, gw_._nbrs, 0.6, 1), 0, 1))
+    assert exp > 0.05 and sw.sim(0, 1) == pytest.approx(exp, rel=2e-12, abs=0)
     d = tmp_path / "d.txt"
     d.write_text("1 2\n2 3\n")
     gd = GWGraph.from_edgelist(str(d), delimiter=" ", semantics="nx", directed=True)
