@@ -672,7 +672,10 @@ int gw_dev_double_random_walk(gw_graph* g, int sample, int step, double C, uint6
     }
   }
   if (e == hipSuccess) {
-    k_drw_finish<<<(unsigned)((n * n + 255) / 256), 256, 0, s>>>(n, (double)(sample * sample), sim_dev);
+    // SAMPLE * SAMPLE is a Java int product (:90): it wraps to a signed 32-bit value from SAMPLE = 46341
+    // (-2147479015; 0 at 65536), multiplied unsigned here (no signed overflow)
+    const int32_t sq = (int32_t)((uint32_t)sample * (uint32_t)sample);
+    k_drw_finish<<<(unsigned)((n * n + 255) / 256), 256, 0, s>>>(n, (double)sq, sim_dev);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);

@@ -449,10 +449,17 @@ __global__ void __launch_bounds__(TM_BLOCK) k_topsim_m(TmArgs A) {
   }
 }
 
+// *over = 1 (and nothing launched) if the map plus the kernel's static LDS exceed lds_limit (0: unknown)
 template <int STEP>
-hipError_t launch_m(const TmArgs& A, int blocks, size_t lds, hipStream_t s) {
-  hipError_t e = hipFuncSetAttribute((const void*)k_topsim_m<STEP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds);
+hipError_t launch_m(const TmArgs& A, int blocks, size_t lds, size_t lds_limit, int* over, hipStream_t s) {
+  hipFuncAttributes fa;
+  hipError_t e = hipFuncGetAttributes(&fa, (const void*)k_topsim_m<STEP>);
+  if (e != hipSuccess) return e;
+  if (lds_limit != 0 && fa.sharedSizeBytes + lds > lds_limit) {
+    *over = 1;
+    return hipSuccess;
+  }
+  e = hipFuncSetAttribute((const void*)k_topsim_m<STEP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   k_topsim_m<STEP><<<blocks, TM_BLOCK, lds, s>>>(A);
   return hipGetLastError();
@@ -508,8 +515,12 @@ int gw_dev_topsim_m(gw_graph* g, int variant, int capacity, int sample, int step
   // walkers per level, walkers persist -> SAMPLE*(1 + 2L)
   int64_t cap = variant == GW_TOPSIM_SINGLE_RW ? (int64_t)sample * step : (int64_t)sample * (1 + 2 * L) + 16;
   int dev_cus = 256;
+  size_t lds_limit = 0;  // LDS one workgroup may ask for (opt-in)
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, g->device) == hipSuccess) dev_cus = prop.multiProcessorCount;
+  if (hipGetDeviceProperties(&prop, g->device) == hipSuccess) {
+    dev_cus = prop.multiProcessorCount;
+    lds_limit = std::max(prop.sharedMemPerBlock, prop.sharedMemPerBlockOptin);
+  }
   const int64_t per_block = variant == GW_TOPSIM_SINGLE_RW ? cap * 8
                                                             : (int64_t)(L + 1) * cap * 12 + 2 * cap * 8 +
                                                                   2 * (cap + 1) * 4 + cap * 8;
@@ -519,8 +530,10 @@ int gw_dev_topsim_m(gw_graph* g, int variant, int capacity, int sample, int step
     g->err = "TopSim_M workspace exceeds the 16 GB budget";
     return GW_ERR_CAPACITY;
   }
+  // key index: load <= 0.5 (at most `capacity` keys are ever indexed, stale drained ones included), so
+  // capacity 4096 takes 8192 slots: 4097*8 + 8192*8 = 98,312 B
   int hash_slots = 4;
-  while (hash_slots < 2 * (capacity + 1)) hash_slots <<= 1;
+  while (hash_slots < 2 * capacity) hash_slots <<= 1;
   const size_t lds = (size_t)(capacity + 1) * 8 + (size_t)hash_slots * 8;
   TmArgs A{};
   A.G = g->d;
@@ -554,16 +567,17 @@ int gw_dev_topsim_m(gw_graph* g, int variant, int capacity, int sample, int step
   }
   hipError_t e = hipMemsetAsync(A.src_counter, 0, sizeof(unsigned int), s);
   if (e == hipSuccess) e = hipMemsetAsync(A.error_flag, 0, sizeof(int), s);
+  int over = 0;
   if (e == hipSuccess) {
     switch (step) {
-      case 1: e = launch_m<1>(A, (int)blocks, lds, s); break;
-      case 2: e = launch_m<2>(A, (int)blocks, lds, s); break;
-      case 3: e = launch_m<3>(A, (int)blocks, lds, s); break;
-      case 4: e = launch_m<4>(A, (int)blocks, lds, s); break;
-      case 5: e = launch_m<5>(A, (int)blocks, lds, s); break;
-      case 6: e = launch_m<6>(A, (int)blocks, lds, s); break;
-      case 7: e = launch_m<7>(A, (int)blocks, lds, s); break;
-      default: e = launch_m<8>(A, (int)blocks, lds, s); break;
+      case 1: e = launch_m<1>(A, (int)blocks, lds, lds_limit, &over, s); break;
+      case 2: e = launch_m<2>(A, (int)blocks, lds, lds_limit, &over, s); break;
+      case 3: e = launch_m<3>(A, (int)blocks, lds, lds_limit, &over, s); break;
+      case 4: e = launch_m<4>(A, (int)blocks, lds, lds_limit, &over, s); break;
+      case 5: e = launch_m<5>(A, (int)blocks, lds, lds_limit, &over, s); break;
+      case 6: e = launch_m<6>(A, (int)blocks, lds, lds_limit, &over, s); break;
+      case 7: e = launch_m<7>(A, (int)blocks, lds, lds_limit, &over, s); break;
+      default: e = launch_m<8>(A, (int)blocks, lds, lds_limit, &over, s); break;
     }
   }
   int flag = 0;
@@ -572,6 +586,10 @@ int gw_dev_topsim_m(gw_graph* g, int variant, int capacity, int sample, int step
   tm_free(A.qv); tm_free(A.qp); tm_free(A.qw); tm_free(A.qm); tm_free(A.co); tm_free(A.nw);
   tm_free(A.uk); tm_free(A.uvv); tm_free(A.src_counter); tm_free(A.error_flag);
   GW_HIP_TRY(e);
+  if (over) {
+    g->err = "FixedCacheMap capacity does not fit the device's LDS (map and key index are LDS-resident)";
+    return GW_ERR_UNSUPPORTED;
+  }
   if (flag) {
     g->err = "TopSim_M: a BFS level exceeded its queue capacity";
     return GW_ERR_CAPACITY;

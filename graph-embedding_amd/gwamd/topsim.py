@@ -329,7 +329,8 @@ class TopSim_doubleSample(_DoubleBase):
 
 
 class DoubleRandomWalk(_DoubleBase):
-    """simrank.DoubleRandomWalk (DoubleRandomWalk.java:15-95)."""
+    """simrank.DoubleRandomWalk (DoubleRandomWalk.java:15-95).  The divisor SAMPLE * SAMPLE is the Java int
+    product (:90): from SAMPLE = 46341 it wraps to a signed 32-bit value (-2147479015; 0 at 65536)."""
 
     def __init__(self, g, sample, step, C_=C_DEFAULT, seed=0):
         super().__init__(g, C_, seed)

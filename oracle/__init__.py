@@ -59,6 +59,8 @@ def lib():
         L.or_topsim_double_sims.argtypes = [i64, v, ci, d, v, ci]
         L.or_topsim_dev.argtypes = [i64, v, v, ci, ci, d, u64, v, ci, v, ci]
         L.or_double_random_walk.argtypes = [i64, v, v, ci, ci, d, u64, v, ci]
+        L.or_java_int_square.argtypes = [i32]
+        L.or_java_int_square.restype = i32
         L.or_fcm_run.restype = ci
         L.or_simrank_round_rows.argtypes = [i64, v, v, d, v, i64, i64, v, ci]
         L.or_simrank_round_rows.restype = i64
@@ -274,6 +276,11 @@ def double_random_walk(offsets, nbrs, sample, step, C=0.6, seed=0, nthreads=0):
     lib().or_double_random_walk(n, _p(off), _p(nb), int(sample), int(step), float(C), int(seed), _p(sim),
                                 int(nthreads))
     return sim
+
+
+def java_int_square(a):
+    """a * a as a Java int (wraps to signed 32 bits): DoubleRandomWalk's SAMPLE * SAMPLE."""
+    return int(lib().or_java_int_square(int(a)))
 
 
 def fcm_run(nmax, keys, vals):

@@ -996,9 +996,14 @@ void or_topsim_dev(int64_t n, const int64_t* off, const int32_t* nbrs, int sampl
   free(Mj);
 }
 
+/* SAMPLE * SAMPLE of DoubleRandomWalk.getSim (:90) is a Java int product: it */
+/* wraps to a signed 32-bit value from SAMPLE = 46341 (0 at 65536);          */
+/* multiplied unsigned here (no signed overflow).                            */
+int32_t or_java_int_square(int32_t a) { return (int32_t)((uint32_t)a * (uint32_t)a); }
+
 /* DoubleRandomWalk (DoubleRandomWalk.java:50-91): SAMPLE walks of STEP      */
 /* steps per vertex (Philox (v, i, step+1)), then for every pair v < w the   */
-/* first-meeting estimator sum cache[t+1] / SAMPLE^2, mirrored.             */
+/* first-meeting estimator sum cache[t+1] / (SAMPLE * SAMPLE), mirrored.     */
 void or_double_random_walk(int64_t n, const int64_t* off, const int32_t* nbrs, int sample, int step, double C,
                            uint64_t seed, double* sim, int nthreads) {
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ GW_TAG_TOPSIM;
@@ -1038,7 +1043,7 @@ void or_double_random_walk(int64_t n, const int64_t* off, const int32_t* nbrs, i
               break;
             }
         }
-      double val = result / ((double)sample * (double)sample);
+      double val = result / (double)or_java_int_square(sample);
       sim[v * n + w] = val;
       sim[w * n + v] = val;
     }
