@@ -10,6 +10,9 @@ Host-side mirror of the reference interfaces over the libgraphwalk C ABI
 * `gwamd.deepsim`   — DeepSim/src/DeepSim.py (main, save_embeddings): the SimRank-guided
                       net trained on the device-resident walks and SimRank rows;
                       `python -m gwamd.deepsim` takes DeepSim/src/main.py's flags
+* `gwamd.classify`  — classify.scoring (node2vec/src/classify.py): one-vs-rest logistic
+                      regression on the device-resident embedding, top-k prediction,
+                      micro- / macro-F1; `python -m gwamd.classify --emb X --groups G`
 * `gwamd.topsim`    — DeepSim/TopSimAll structures.Graph, TopSim_singleSample,
                       TopSim_Enumerate, SingleRandomWalk, SimRank (naive),
                       Print.printByOrder/printByOrderAll,
@@ -20,7 +23,8 @@ Host-side mirror of the reference interfaces over the libgraphwalk C ABI
 """
 from . import _lib
 from ._lib import device_count, lib
+from . import classify
 from .graph import GWGraph
 
-__all__ = ["GWGraph", "device_count", "lib", "_lib"]
+__all__ = ["GWGraph", "classify", "device_count", "lib", "_lib"]
 __version__ = "0.1.0"

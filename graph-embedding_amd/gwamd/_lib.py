@@ -122,6 +122,28 @@ class DeepSimParams(ctypes.Structure):
                          beta1, beta2, epsilon, score_scale, seed)
 
 
+OVR_CONST_NEG = 0
+OVR_CONST_POS = 1
+OVR_FITTED = 2
+OVR_NOT_CONVERGED = 3
+
+
+class OvrParams(ctypes.Structure):
+    """gw_ovr_params_t (include/graphwalk.h); struct_size is filled in by default."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("dim", ctypes.c_int32), ("labels", ctypes.c_int32),
+                ("max_newton", ctypes.c_int32), ("max_cg", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+                ("C", ctypes.c_double), ("gtol", ctypes.c_double), ("seed", ctypes.c_uint64)]
+
+    def __init__(self, labels=0, dim=128, max_newton=100, max_cg=200, C=1.0, gtol=1e-8, seed=0):
+        super().__init__(ctypes.sizeof(OvrParams), dim, labels, max_newton, max_cg, 0, C, gtol, seed)
+
+
+class OvrStats(ctypes.Structure):
+    """gw_ovr_stats_t."""
+    _fields_ = [("passes", ctypes.c_int64), ("fitted", ctypes.c_int32), ("constant", ctypes.c_int32),
+                ("not_converged", ctypes.c_int32), ("newton_max", ctypes.c_int32)]
+
+
 P = ctypes.c_void_p
 I32 = ctypes.c_int32
 I64 = ctypes.c_int64
@@ -213,6 +235,17 @@ SIGNATURES = {
     "gw_deepsim_vectors_dev": (ctypes.c_int, [P, PP, PI64]),
     "gw_deepsim_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
     "gw_write_deepsim_text": (ctypes.c_int, [CP, P, I64, ctypes.c_int]),
+    "gw_ovr_create": (ctypes.c_int, [ctypes.c_int, I64, ctypes.POINTER(OvrParams), PP]),
+    "gw_ovr_free": (ctypes.c_int, [P]),
+    "gw_ovr_last_error": (CP, [P]),
+    "gw_ovr_set_features": (ctypes.c_int, [P, P, I64]),
+    "gw_ovr_set_labels": (ctypes.c_int, [P, P, P]),
+    "gw_ovr_order": (ctypes.c_int, [U64, U64, I64, P]),
+    "gw_ovr_fit": (ctypes.c_int, [P, P, I64, ctypes.POINTER(OvrStats), P]),
+    "gw_ovr_score": (ctypes.c_int, [P, P, I64, P, P]),
+    "gw_ovr_decision": (ctypes.c_int, [P, P, I64, P]),
+    "gw_ovr_export": (ctypes.c_int, [P, P, P, P, P]),
+    "gw_ovr_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
     "gw_comm_unique_id": (ctypes.c_int, [P]),
     "gw_comm_init": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, PP]),
     "gw_comm_allgather": (ctypes.c_int, [P, P, P, I64, ctypes.c_int, P]),
@@ -240,13 +273,15 @@ def lib():
     return _lib
 
 
-def check(rc, handle=None, sgns=None, deepsim=None):
+def check(rc, handle=None, sgns=None, deepsim=None, ovr=None):
     """Raise for a failing status; `handle` a gw_graph, `sgns` a gw_sgns, `deepsim` a gw_deepsim or True for a
-    handle-less gw_deepsim call (for the message)."""
+    handle-less gw_deepsim call, `ovr` likewise for gw_ovr (for the message)."""
     if rc == GW_OK:
         return
     L = lib()
-    if deepsim is not None:
+    if ovr is not None:
+        msg = L.gw_ovr_last_error(None if ovr is True else ovr)
+    elif deepsim is not None:
         msg = L.gw_deepsim_last_error(None if deepsim is True else deepsim)
     else:
         msg = L.gw_sgns_last_error(sgns) if sgns is not None else L.gw_last_error(handle)

@@ -12,6 +12,8 @@ main.py:92-101: skip-gram with negative sampling, --dimensions, --window-size,
 save_word2vec_format's text form; in scale mode the walks stay in HBM between
 the two steps.  --workers is accepted and unused (the trainer sizes its own
 concurrency).  Without --output only the walks are produced, as before.
+With --groups (and --output) the embeddings are then scored where they lie in
+HBM (classify.scoring: one-vs-rest logistic regression, micro- and macro-F1).
 Walks are written in DeepSim's save_list format (DeepSim/src/main.py:237-243)
 or as .npy.
 
@@ -43,6 +45,8 @@ def parse_args(argv=None, p=1.0, q=1.0):
     ap.add_argument("--input", nargs="?", default="../graph/karate.edgelist", help="Input graph path")
     ap.add_argument("--output", nargs="?", default=None, help="Embeddings path (word2vec text format); trained on the GPU after the walks, "
                          "on rank 0 only when launched with several ranks.  Omitted: walks only")
+    ap.add_argument("--groups", default=None, help="lines `node,label`: with --output, score the embeddings where they lie in "
+                         "HBM by one-vs-rest logistic regression F1 (gwamd.classify.scoring)")
     ap.add_argument("--walks", default="walks.txt", help="walks output (save_list format, or .npy)")
     ap.add_argument("--dimensions", type=int, default=128)
     ap.add_argument("--walk-length", type=int, default=80)
@@ -196,6 +200,9 @@ def _embed(args, walks, labels, device):
                            negative=args.negative, sample=args.sample, seed=args.seed, device=device)
     emb.save_word2vec_format(args.output)
     print(f"{len(emb.index2word)} x {args.dimensions} embeddings -> {args.output}", file=sys.stderr)
+    if args.groups:
+        from . import classify
+        classify.scoring(emb, classify.read_groups(args.groups), seed=args.seed, device=device)
 
 
 def main(argv=None):

@@ -231,6 +231,8 @@ def parse_args(argv=None):
     ap.add_argument("--input", nargs="?", default="../../data/BlogCatalog-dataset/data/edges.txt")
     ap.add_argument("--simrank_path", nargs="?", default="../output_u_u/SimRank/blog_simrank_navie_top20.txt.sim.txt")
     ap.add_argument("--emb_output", nargs="?", default="../emb/blog.emb")
+    ap.add_argument("--groups", default=None, help="lines `node,label` (node = embedding row): score the embedding "
+                                                   "where it lies in HBM (main.py:287-289, classify.scoring)")
     ap.add_argument("--TOPK", default=1000, type=int)
     ap.add_argument("--vertex-num", type=int, default=10313)
     ap.add_argument("--dimensions", type=int, default=128)
@@ -289,6 +291,10 @@ def cli(argv=None):
         walks, labels = _generate_walks(args)
     m = main(args, simrank, walks, labels)
     print(f"{m.V} x {args.dimensions} embeddings -> {args.emb_output}", file=sys.stderr)
+    if args.groups:
+        from . import classify
+        _, _, row_off, ids = classify.groups_csr(classify.read_groups(args.groups), range(m.V))
+        classify.scoring(m, (row_off, ids), seed=args.seed, device=args.device)
     return 0
 
 

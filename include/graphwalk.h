@@ -665,6 +665,118 @@ int gw_deepsim_kernel_attrs(gw_deepsim* m, int cap, const char** names, int32_t*
  * 1e-4 <= |x| < 1e16, else scientific with a two-digit exponent).             */
 int gw_write_deepsim_text(const char* path, const float* w1, int64_t n, int dim);
 
+/* ---- scoring: one-vs-rest logistic regression, top-k prediction, F1 ---------- */
+/* Replaces classify.scoring (node2vec/src/classify.py, DeepSim/src/classify.py):
+ * TopKRanker(LogisticRegression(penalty='l2')) fitted one-vs-rest on a share of
+ * the embedding rows, as many labels predicted per held-out row as it really
+ * has, micro- and macro-F1.  csrc/gw_ovr_law.h holds the one definition the
+ * kernels and the host evaluation (device = -1) share; they agree bit for bit
+ * (tested).
+ *   problem     per label c over the training rows T, x~ = (x, 1), s = +-1:
+ *               f_c(w) = 1/2 w.w + C * sum_{i in T} log(1 + exp(-s_ic w.x~_i)),
+ *               liblinear's primal L2 logistic regression as the reference's
+ *               sklearn ran it (C = 1, bias regularised, intercept_scaling 1);
+ *               the minimiser is unique.
+ *   constant    a label with no positive, or no negative, training row is not
+ *               fitted: its decision value is -inf / +inf (sklearn's
+ *               _ConstantPredictor).
+ *   arithmetic  features are the caller's fp32 widened, everything else fp64;
+ *               only + - * /, sqrt and the law's own exp (range reduction by
+ *               ln 2, degree-13 Taylor polynomial, all in explicit fma), built
+ *               with -ffp-contract=off; no libm on either side.
+ *   solver      Newton-CG from w = 0.  Per Newton step: CG on
+ *               (I + C X~'DX~) s = -g from s = 0, stopped at |r| <= 0.1 |g| or
+ *               after max_cg products; then w + alpha s, alpha = 1, 1/2, ...
+ *               (at most 30 halvings) until |grad| decreases strictly - the
+ *               merit is the gradient norm, so no logarithm is needed, and
+ *               g.H s <= -0.9 |g|^2 makes a small step acceptable.  Stop:
+ *               |grad f_c(w)| <= gtol * |grad f_c(0)|; a label that has not met
+ *               it after max_newton accepted steps (or 30 halvings) is
+ *               reported GW_OVR_NOT_CONVERGED.  All labels of a fit advance
+ *               together through shared passes over the gathered rows (one
+ *               pass = for every running label either the gradient at its
+ *               trial point or one Hessian-vector product); a finished label
+ *               is frozen, and no label's arithmetic reads another's, so a
+ *               label fitted alone gives the same bits.
+ *   sum orders  x~.v: fma over the dim columns ascending from +0, then + v[dim];
+ *               coefficient * x~ summed over the rows of a block of 64 gathered
+ *               rows ascending (fma from +0), blocks then added ascending; dot
+ *               products over the dim + 1 entries ascending (fma from +0).
+ *               Nothing depends on the grid.
+ *   prediction  a row with k true labels gets the k labels of largest decision
+ *               value w.x~ (not the sigmoid, which saturates); k = 0 predicts
+ *               nothing; of equal values the larger label index wins, which is
+ *               argsort()[-k:] under a stable sort (numpy's default sort
+ *               promises no order among equals).
+ *   counts      tp, fp, fn per label over the scored rows; micro = 2 sum tp /
+ *               (2 sum tp + sum fp + sum fn); macro = mean over all labels of
+ *               2 tp / (2 tp + fp + fn), 0 where that is 0 / 0.  (The
+ *               reference's old sklearn averaged over the labels present in
+ *               truth or prediction: form it from the same counts.)
+ *   shuffle     order[i] = gw_feistel_perm(i, n, seed low ^ shuffle low,
+ *               seed high ^ "ovS0", tweak = shuffle high); the reference's
+ *               skshuffle is unseeded.
+ * Device path: dim <= 1024 and labels <= 1024 (else GW_ERR_UNSUPPORTED); the
+ * host path takes any size.  HBM of a fit over T rows: 17 * T * labels bytes
+ * (y, z, D), 8 * ceil(T / 64) * labels * (dim + 1) of block partials.         */
+#define GW_OVR_CONST_NEG 0     /* no positive training row: decision -inf      */
+#define GW_OVR_CONST_POS 1     /* no negative training row: decision +inf      */
+#define GW_OVR_FITTED 2        /* met the stop condition                       */
+#define GW_OVR_NOT_CONVERGED 3 /* weights are the last accepted iterate        */
+typedef struct gw_ovr gw_ovr;
+typedef struct gw_ovr_params_t {
+  int32_t struct_size; /* as gw_sgns_params_t.struct_size                      */
+  int32_t dim;         /* columns read of a feature row (128)                  */
+  int32_t labels;      /* L (required)                                         */
+  int32_t max_newton;  /* accepted Newton steps per label (100)                */
+  int32_t max_cg;      /* Hessian-vector products per Newton step (200)        */
+  int32_t reserved0;   /* 0                                                    */
+  double C;            /* 1.0                                                  */
+  double gtol;         /* 1e-8                                                 */
+  uint64_t seed;       /* 0: not used by the fit; kept for gw_ovr_order callers */
+} gw_ovr_params_t;
+typedef struct gw_ovr_stats_t {
+  int64_t passes;        /* shared passes over the training rows               */
+  int32_t fitted;        /* labels per final state                             */
+  int32_t constant;
+  int32_t not_converged;
+  int32_t newton_max;    /* largest accepted-step count of a label             */
+} gw_ovr_stats_t;
+/* device >= 0: a GPU; -1: the host evaluation.  n = rows of the feature matrix */
+int gw_ovr_create(int device, int64_t n, const gw_ovr_params_t* params, gw_ovr** out);
+int gw_ovr_free(gw_ovr* m);
+const char* gw_ovr_last_error(const gw_ovr* m);
+/* Row v at x + v * pitch floats (pitch >= dim): device memory for device >= 0,
+ * read where it lies (zero-copy from gw_sgns_vectors_dev /
+ * gw_deepsim_vectors_dev), host memory for device = -1.  It must outlive the
+ * calls; only dim floats of a row are ever read.                             */
+int gw_ovr_set_features(gw_ovr* m, const float* x, int64_t pitch);
+/* Host CSR of the true labels: row v has ids[row_off[v] .. row_off[v + 1]),
+ * distinct within a row.  An id outside [0, labels) gives GW_ERR_RANGE.       */
+int gw_ovr_set_labels(gw_ovr* m, const int64_t* row_off, const int32_t* ids);
+/* The law's permutation of [0, n) for (seed, shuffle) into order[n] (host)    */
+int gw_ovr_order(uint64_t seed, uint64_t shuffle, int64_t n, int64_t* order);
+/* Fits every label on the rows order[0 .. train_count) (host array),
+ * 1 <= train_count <= n; a row outside [0, n) gives GW_ERR_RANGE, a repeated
+ * one GW_ERR_INVALID.  stats is optional.  Runs on `stream` and synchronises
+ * it.  GW_ERR_STATE before set_features and set_labels; a failing fit leaves
+ * the handle unfitted.                                                        */
+int gw_ovr_fit(gw_ovr* m, const int64_t* order, int64_t train_count, gw_ovr_stats_t* stats, void* stream);
+/* Predicts rows[0 .. count) (host array, count >= 0) by the top-k rule and
+ * counts on the device: counts[labels][3] = tp, fp, fn (host).  GW_ERR_STATE
+ * before gw_ovr_fit.                                                          */
+int gw_ovr_score(gw_ovr* m, const int64_t* rows, int64_t count, int64_t* counts, void* stream);
+/* Host copy of the decision values z[count][labels] of rows (tests)           */
+int gw_ovr_decision(gw_ovr* m, const int64_t* rows, int64_t count, double* z);
+/* Host copies (NULL skips): W[labels][dim + 1] (bias last; 0 for a constant
+ * label), state[labels] (GW_OVR_*), newton_iters[labels], gnorm[labels]
+ * (the law's own |grad f_c(w)| at the returned weights).                      */
+int gw_ovr_export(gw_ovr* m, double* W, int32_t* state, int32_t* newton_iters, double* gnorm);
+/* Per kernel (up to `cap`): name, registers per lane, scratch bytes per lane,
+ * LDS bytes per workgroup; *count = kernels.                                  */
+int gw_ovr_kernel_attrs(gw_ovr* m, int cap, const char** names, int32_t* vgprs, int32_t* scratch_bytes,
+                        int32_t* lds_bytes, int32_t* count);
+
 /* ---- multi-GPU exchange (RCCL over xGMI) ---------------------------------- */
 /* the graph is replicated and units (walks, TopSim sources) are
  * sharded by global index with no data-path collective; the only exchange is
