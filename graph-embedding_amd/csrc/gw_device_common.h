@@ -4,6 +4,8 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
+#include <vector>
 
 #include "gw_internal.h"
 #include "gw_philox.h"
@@ -16,6 +18,128 @@
       return GW_ERR_DEVICE;                                                  \
     }                                                                        \
   } while (0)
+
+// Frees and nulls a buffer that a handle owns (a call's own buffers: gw_dev_scratch).
+template <typename T>
+void gw_dev_free(T*& p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+
+// Device scratch that lives for one call: every buffer it hands out is freed
+// when it goes out of scope, on every return path.  A failed allocation puts
+// `what` into g->err (nullptr: the byte count and the HIP error string; g may
+// be nullptr where the caller reports errors itself) and returns GW_ERR_NOMEM.
+class gw_dev_scratch {
+ public:
+  explicit gw_dev_scratch(gw_graph* g, const char* what = nullptr) : g_(g), what_(what) {}
+  gw_dev_scratch(const gw_dev_scratch&) = delete;
+  gw_dev_scratch& operator=(const gw_dev_scratch&) = delete;
+  ~gw_dev_scratch() {
+    for (void* p : bufs_) (void)hipFree(p);
+  }
+
+  static std::string alloc_error(size_t bytes, hipError_t e) {
+    return std::string("hipMalloc(workspace ") + std::to_string(bytes) + " B): " + hipGetErrorString(e);
+  }
+
+  // count < 1 allocates one element
+  template <typename T>
+  int alloc(T** p, int64_t count) {
+    *p = nullptr;
+    if (count < 1) count = 1;
+    void* q = nullptr;
+    hip_error_ = hipMalloc(&q, sizeof(T) * (size_t)count);
+    if (hip_error_ != hipSuccess) {
+      (void)hipGetLastError();
+      if (g_) g_->err = what_ ? std::string(what_) : alloc_error(sizeof(T) * (size_t)count, hip_error_);
+      return GW_ERR_NOMEM;
+    }
+    bufs_.push_back(q);
+    *p = static_cast<T*>(q);
+    return GW_OK;
+  }
+
+  // one buffer before the scope ends (a caller that regrows it)
+  template <typename T>
+  void free(T*& p) {
+    for (void*& q : bufs_)
+      if (q == p) {
+        q = bufs_.back();
+        bufs_.pop_back();
+        (void)hipFree(p);
+        break;
+      }
+    p = nullptr;
+  }
+
+  // what hipMalloc returned to the last alloc()
+  hipError_t hip_error() const { return hip_error_; }
+
+ private:
+  gw_graph* g_;
+  const char* what_;
+  hipError_t hip_error_ = hipSuccess;
+  std::vector<void*> bufs_;
+};
+
+// Runtime step -> compile-time constant: f(std::integral_constant<int, S>{})
+// for step S in 1..7 and S = 8 otherwise (callers validate step first).
+template <typename F>
+auto gw_with_step(int step, F&& f) {
+  switch (step) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
+
+// Exclusive scan of v over a workgroup of NW waves; s_wave holds NW + 1
+// values.  Every thread gets the workgroup's sum in *total.
+template <int NW, typename T = int>
+__device__ __forceinline__ T block_excl_scan(T v, T* s_wave, T* total) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  T x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    T y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) s_wave[wid] = x;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    T acc = 0;
+    for (int w = 0; w < NW; ++w) {
+      T t = s_wave[w];
+      s_wave[w] = acc;
+      acc += t;
+    }
+    s_wave[NW] = acc;
+  }
+  __syncthreads();
+  T r = s_wave[wid] + x - v;
+  *total = s_wave[NW];
+  __syncthreads();
+  return r;
+}
+
+// first index i in [0, n) with a[i] > x  (a non-decreasing)
+__device__ __forceinline__ int upper_bound_i32(const int32_t* a, int n, int x) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    int mid = (lo + hi) >> 1;
+    if (a[mid] <= x)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
 
 // Binary search for `key` in the sorted row nbrs[b, e); returns the slot or
 // -1.  Rows of NX_SIMPLE graphs are sorted by dense id (== label order), see

@@ -888,10 +888,10 @@ int gw_dev_alias_setup(int device, const double* probs, int64_t K, int64_t* J,
   double *dp = nullptr, *dq = nullptr;
   int64_t* dJ = nullptr;
   int32_t* st = nullptr;
-  hipError_t e = hipMalloc((void**)&dp, K * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&dq, K * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&dJ, K * sizeof(int64_t));
-  if (e == hipSuccess) e = hipMalloc((void**)&st, K * sizeof(int32_t));
+  gw_dev_scratch scratch(nullptr);
+  hipError_t e = hipSuccess;
+  if (scratch.alloc(&dp, K) || scratch.alloc(&dq, K) || scratch.alloc(&dJ, K) || scratch.alloc(&st, K))
+    e = scratch.hip_error();
   if (e == hipSuccess) e = hipMemcpy(dp, probs, K * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     k_alias_single<<<1, 64>>>(dp, K, dJ, dq, st);
@@ -899,10 +899,6 @@ int gw_dev_alias_setup(int device, const double* probs, int64_t K, int64_t* J,
   }
   if (e == hipSuccess) e = hipMemcpy(J, dJ, K * sizeof(int64_t), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(q, dq, K * sizeof(double), hipMemcpyDeviceToHost);
-  if (dp) (void)hipFree(dp);
-  if (dq) (void)hipFree(dq);
-  if (dJ) (void)hipFree(dJ);
-  if (st) (void)hipFree(st);
   if (e != hipSuccess) {
     *err = hipGetErrorString(e);
     return GW_ERR_DEVICE;
@@ -1109,16 +1105,15 @@ extern "C" int gw_philox4x32(int device, const uint32_t* in, int64_t n, uint32_t
   if (device >= count) return gw_fail(nullptr, GW_ERR_INVALID, "device ordinal out of range");
   GW_GUARD_DEVICE(nullptr, device);
   uint32_t *d_in = nullptr, *d_out = nullptr;
-  hipError_t e = hipMalloc((void**)&d_in, sizeof(uint32_t) * 6 * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_out, sizeof(uint32_t) * 4 * (size_t)n);
+  gw_dev_scratch scratch(nullptr);
+  hipError_t e = hipSuccess;
+  if (scratch.alloc(&d_in, 6 * n) || scratch.alloc(&d_out, 4 * n)) e = scratch.hip_error();
   if (e == hipSuccess) e = hipMemcpy(d_in, in, sizeof(uint32_t) * 6 * (size_t)n, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     k_philox<<<grid_for(n), kBlock>>>(d_in, n, d_out);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(uint32_t) * 4 * (size_t)n, hipMemcpyDeviceToHost);
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
   if (e != hipSuccess) return gw_fail(nullptr, GW_ERR_DEVICE, "%s", hipGetErrorString(e));
   return GW_OK;
 }

@@ -249,22 +249,16 @@ hipError_t launch_pass(const SrArgs& A, const double* src, double* dst, int last
   return hipGetLastError();
 }
 
-template <typename T>
-void sr_free(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
 }  // namespace
 
 void gw_dev_simrank_release(gw_graph* g) {
-  sr_free(g->sr_work);
-  sr_free(g->sr_x);
-  sr_free(g->sr_ent);
-  sr_free(g->sr_heads);
-  sr_free(g->sr_off);
-  sr_free(g->sr_poff);
-  sr_free(g->sr_rows);
+  gw_dev_free(g->sr_work);
+  gw_dev_free(g->sr_x);
+  gw_dev_free(g->sr_ent);
+  gw_dev_free(g->sr_heads);
+  gw_dev_free(g->sr_off);
+  gw_dev_free(g->sr_poff);
+  gw_dev_free(g->sr_rows);
   g->sr_n = 0;
   g->sr_m = 0;
 }
@@ -386,14 +380,11 @@ extern "C" int gw_simrank_naive_host(gw_graph* g, double C, int iters, double* s
   const int64_t n = g->n;
   if (n == 0) return GW_OK;
   double* d_sim = nullptr;
-  if (hipMalloc((void**)&d_sim, (size_t)n * n * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    return gw_fail(g, GW_ERR_NOMEM, "n*n result does not fit in device memory");
-  }
+  gw_dev_scratch scratch(g);
+  if (scratch.alloc(&d_sim, n * n)) return gw_fail(g, GW_ERR_NOMEM, "n*n result does not fit in device memory");
   int rc = gw_dev_simrank_naive(g, C, iters, d_sim, nullptr);
   hipError_t e = hipSuccess;
   if (rc == GW_OK) e = hipMemcpy(sim, d_sim, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(d_sim);
   if (rc != GW_OK) return rc;
   if (e != hipSuccess) return gw_fail(g, GW_ERR_DEVICE, "%s", hipGetErrorString(e));
   return GW_OK;

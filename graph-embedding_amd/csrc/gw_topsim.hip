@@ -98,33 +98,6 @@ struct TsArgs {
   unsigned long long* phase;  // diagnostics (GW_DIAG_TS_PHASES): cycles per phase, thread 0 of each block
 };
 
-template <int NW = TS_WAVES, typename T = int>
-__device__ __forceinline__ T block_excl_scan(T v, T* s_wave, T* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  T x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    T y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_wave[wid] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    T acc = 0;
-    for (int w = 0; w < NW; ++w) {
-      T t = s_wave[w];
-      s_wave[w] = acc;
-      acc += t;
-    }
-    s_wave[NW] = acc;
-  }
-  __syncthreads();
-  T r = s_wave[wid] + x - v;
-  *total = s_wave[NW];
-  __syncthreads();
-  return r;
-}
-
 template <typename T, int NW = TS_WAVES>
 __device__ __forceinline__ T block_sum(T v, T* s_red) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -134,19 +107,6 @@ __device__ __forceinline__ T block_sum(T v, T* s_red) {
   for (int w = 0; w < NW; ++w) r += s_red[w];
   __syncthreads();
   return r;
-}
-
-// first index i in [0, n) with a[i] > x  (a non-decreasing)
-__device__ __forceinline__ int upper_bound_i32(const int32_t* a, int n, int x) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    int mid = (lo + hi) >> 1;
-    if (a[mid] <= x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
 }
 
 // one wave: the radix bin holding the need-th key, scanning the 256 bins
@@ -1974,13 +1934,14 @@ __global__ void __launch_bounds__(TS_BLOCK) k_topsim_pipe_row(TsArgs A) {
   topsim_body<STEP, 0, TS_BLOCK, true>(A);
 }
 
+// the handle-owned workspace (gw_topsim_ws): lives until the next prepare
 template <typename T>
 int ws_alloc(gw_graph* g, T** p, int64_t count) {
   *p = nullptr;
   if (count <= 0) count = 1;
   hipError_t e = hipMalloc((void**)p, sizeof(T) * (size_t)count);
   if (e != hipSuccess) {
-    g->err = std::string("hipMalloc(workspace ") + std::to_string(sizeof(T) * (size_t)count) + " B): " + hipGetErrorString(e);
+    g->err = gw_dev_scratch::alloc_error(sizeof(T) * (size_t)count, e);
     *p = nullptr;
     return GW_ERR_NOMEM;
   }
@@ -1998,83 +1959,41 @@ __global__ void k_ts_ent(gw_dev_graph G, gw_ts_ent* __restrict__ ent) {
   ent[e] = v;
 }
 
-template <typename T>
-void ws_free(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
 constexpr size_t TS_2WG_LDS = 72 * 1024;  // dynamic LDS that still lets two workgroups share a CU
 
-template <int STEP, int MODE, bool TWO>
-hipError_t launch_step(const TsArgs& A, int blocks, size_t lds, hipStream_t s) {
-  const void* fn = TWO ? (const void*)k_topsim_2wg<STEP, MODE> : (const void*)k_topsim<STEP, MODE>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  if (TWO)
-    k_topsim_2wg<STEP, MODE><<<blocks, TS_BLOCK, lds, s>>>(A);
-  else
-    k_topsim<STEP, MODE><<<blocks, TS_BLOCK, lds, s>>>(A);
-  return hipGetLastError();
-}
+// The kernel that (mode, pipe, lds) means at each STEP, by address and by
+// printable name: what launch() runs, gw_topsim_kernel_attrs inspects and
+// gw_topsim_kernel reports.
+struct TsKernel {
+  const void* fn;
+  std::string name;
+};
 
 template <int STEP>
-hipError_t launch_mode(int mode, bool pipe, const TsArgs& A, int blocks, size_t lds, hipStream_t s) {
-  if (mode == 2 && pipe) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_topsim_pipe<STEP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return e;
-    k_topsim_pipe<STEP><<<blocks, TS_BLOCK, lds, s>>>(A);
-    return hipGetLastError();
-  }
-  if (mode == 0 && pipe) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_topsim_pipe_row<STEP>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    k_topsim_pipe_row<STEP><<<blocks, TS_BLOCK, lds, s>>>(A);
-    return hipGetLastError();
-  }
-  if (mode == 2) return launch_step<STEP, 2, true>(A, blocks, lds, s);
-  if (mode == 1) return launch_step<STEP, 1, false>(A, blocks, lds, s);
-  return lds <= TS_2WG_LDS ? launch_step<STEP, 0, true>(A, blocks, lds, s) : launch_step<STEP, 0, false>(A, blocks, lds, s);
+TsKernel ts_kernel(int mode, bool pipe, size_t lds) {
+  const std::string s = std::to_string(STEP);
+  if (mode == 2 && pipe) return {(const void*)k_topsim_pipe<STEP>, "k_topsim_pipe<" + s + ">"};
+  if (mode == 0 && pipe) return {(const void*)k_topsim_pipe_row<STEP>, "k_topsim_pipe_row<" + s + ">"};
+  if (mode == 2) return {(const void*)k_topsim_2wg<STEP, 2>, "k_topsim_2wg<" + s + ", 2>"};
+  if (mode == 1) return {(const void*)k_topsim<STEP, 1>, "k_topsim<" + s + ", 1>"};
+  if (lds <= TS_2WG_LDS) return {(const void*)k_topsim_2wg<STEP, 0>, "k_topsim_2wg<" + s + ", 0>"};
+  return {(const void*)k_topsim<STEP, 0>, "k_topsim<" + s + ", 0>"};
 }
 
-// the kernel launch_mode() dispatches (gw_topsim_kernel_attrs)
-template <int STEP>
-const void* kernel_fn(int mode, bool pipe, size_t lds) {
-  if (mode == 2 && pipe) return (const void*)k_topsim_pipe<STEP>;
-  if (mode == 0 && pipe) return (const void*)k_topsim_pipe_row<STEP>;
-  if (mode == 2) return (const void*)k_topsim_2wg<STEP, 2>;
-  if (mode == 1) return (const void*)k_topsim<STEP, 1>;
-  return lds <= TS_2WG_LDS ? (const void*)k_topsim_2wg<STEP, 0> : (const void*)k_topsim<STEP, 0>;
-}
-
-const void* kernel_fn(int step, int mode, bool pipe, size_t lds) {
-  switch (step) {
-    case 1: return kernel_fn<1>(mode, pipe, lds);
-    case 2: return kernel_fn<2>(mode, pipe, lds);
-    case 3: return kernel_fn<3>(mode, pipe, lds);
-    case 4: return kernel_fn<4>(mode, pipe, lds);
-    case 5: return kernel_fn<5>(mode, pipe, lds);
-    case 6: return kernel_fn<6>(mode, pipe, lds);
-    case 7: return kernel_fn<7>(mode, pipe, lds);
-    case 8: return kernel_fn<8>(mode, pipe, lds);
-    default: return nullptr;
-  }
+// fn == nullptr for a step outside 1..8
+TsKernel ts_kernel(int step, int mode, bool pipe, size_t lds) {
+  if (step < 1 || step > 8) return {nullptr, ""};
+  return gw_with_step(step, [&](auto S) { return ts_kernel<decltype(S)::value>(mode, pipe, lds); });
 }
 
 hipError_t launch(int step, int mode, bool pipe, const TsArgs& A, int blocks, size_t lds, hipStream_t s) {
-  switch (step) {
-    case 1: return launch_mode<1>(mode, pipe, A, blocks, lds, s);
-    case 2: return launch_mode<2>(mode, pipe, A, blocks, lds, s);
-    case 3: return launch_mode<3>(mode, pipe, A, blocks, lds, s);
-    case 4: return launch_mode<4>(mode, pipe, A, blocks, lds, s);
-    case 5: return launch_mode<5>(mode, pipe, A, blocks, lds, s);
-    case 6: return launch_mode<6>(mode, pipe, A, blocks, lds, s);
-    case 7: return launch_mode<7>(mode, pipe, A, blocks, lds, s);
-    case 8: return launch_mode<8>(mode, pipe, A, blocks, lds, s);
-    default: return hipErrorInvalidValue;
-  }
+  const TsKernel k = ts_kernel(step, mode, pipe, lds);
+  if (!k.fn) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  void* args[] = {const_cast<TsArgs*>(&A)};
+  (void)hipLaunchKernel(k.fn, dim3((unsigned)blocks), dim3(TS_BLOCK), args, lds, s);
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -2149,28 +2068,28 @@ int gw_dev_topsim_prepare(gw_graph* g, int variant, int sample, int step, int to
   }
   GW_HIP_TRY(hipSetDevice(g->device));
   gw_topsim_ws& t = g->ts;
-  ws_free(t.lvl_vertex);
-  ws_free(t.lvl_parent);
-  ws_free(t.lvl_deg);
-  ws_free(t.lvl_off);
-  ws_free(t.lvl_mass);
-  ws_free(t.child_off);
-  ws_free(t.spawn_node);
-  ws_free(t.spawn_level);
-  ws_free(t.spawn_first);
-  ws_free(t.spawn_mass);
-  ws_free(t.acc_row);
-  ws_free(t.ov_list);
-  ws_free(t.touched);
-  ws_free(t.app);
-  ws_free(t.claim);
-  ws_free(t.redo);
-  ws_free(t.enum_tgt);
-  ws_free(t.enum_val);
-  ws_free(t.dsel_id);
-  ws_free(t.dsel_val);
-  ws_free(t.src_counter);
-  ws_free(t.error_flag);
+  gw_dev_free(t.lvl_vertex);
+  gw_dev_free(t.lvl_parent);
+  gw_dev_free(t.lvl_deg);
+  gw_dev_free(t.lvl_off);
+  gw_dev_free(t.lvl_mass);
+  gw_dev_free(t.child_off);
+  gw_dev_free(t.spawn_node);
+  gw_dev_free(t.spawn_level);
+  gw_dev_free(t.spawn_first);
+  gw_dev_free(t.spawn_mass);
+  gw_dev_free(t.acc_row);
+  gw_dev_free(t.ov_list);
+  gw_dev_free(t.touched);
+  gw_dev_free(t.app);
+  gw_dev_free(t.claim);
+  gw_dev_free(t.redo);
+  gw_dev_free(t.enum_tgt);
+  gw_dev_free(t.enum_val);
+  gw_dev_free(t.dsel_id);
+  gw_dev_free(t.dsel_val);
+  gw_dev_free(t.src_counter);
+  gw_dev_free(t.error_flag);
   const int64_t n = g->n;
   const int L = 2 * step;
   int64_t level_cap, spawn_cap;
@@ -2290,14 +2209,7 @@ int gw_dev_topsim_prepare(gw_graph* g, int variant, int sample, int step, int to
   t.app_cap = app_cap;
   t.lds_bytes = lds_row ? (size_t)n * 8 : (size_t)(mode == 2 ? TsHash<2>::SLOTS : TsHash<1>::SLOTS) * 12;
   // the kernel launch() dispatches for this workspace (gw_topsim_kernel)
-  if (mode == 2 && pipe)
-    std::snprintf(t.kernel, sizeof t.kernel, "k_topsim_pipe<%d>", step);
-  else if (mode == 0 && pipe)
-    std::snprintf(t.kernel, sizeof t.kernel, "k_topsim_pipe_row<%d>", step);
-  else if (mode == 2 || (mode == 0 && t.lds_bytes <= TS_2WG_LDS))
-    std::snprintf(t.kernel, sizeof t.kernel, "k_topsim_2wg<%d, %d>", step, mode);
-  else
-    std::snprintf(t.kernel, sizeof t.kernel, "k_topsim<%d, %d>", step, mode);
+  std::snprintf(t.kernel, sizeof t.kernel, "%s", ts_kernel(step, mode, pipe, t.lds_bytes).name.c_str());
   GW_HIP_TRY(hipDeviceSynchronize());
   return GW_OK;
 }
@@ -2377,8 +2289,9 @@ int gw_dev_topsim(gw_graph* g, int variant, int sample, int step, double C, uint
   // GW_DIAG_TS_PHASES=1: cycles per kernel phase summed over blocks, to stderr (diagnostics only)
   const char* dph = GW_DIAG_ENV("GW_DIAG_TS_PHASES");
   A.phase = nullptr;
+  gw_dev_scratch scratch(g);
   if (dph && dph[0] == '1') {
-    GW_HIP_TRY(hipMalloc((void**)&A.phase, 17 * sizeof(unsigned long long)));
+    if (int rc = scratch.alloc(&A.phase, 17)) return rc;
     GW_HIP_TRY(hipMemsetAsync(A.phase, 0, 17 * sizeof(unsigned long long), s));
   }
   // a heavy source's key-hash partition can overflow only when one key that
@@ -2410,7 +2323,6 @@ int gw_dev_topsim(gw_graph* g, int variant, int sample, int step, double C, uint
   if (A.phase) {
     unsigned long long ph[17];
     GW_HIP_TRY(hipMemcpy(ph, A.phase, sizeof ph, hipMemcpyDeviceToHost));
-    (void)hipFree(A.phase);
     const unsigned long long app = ph[10] + ph[11] + ph[12] + ph[13];
     std::fprintf(stderr, "[k_topsim phases, cycles summed over %d blocks] levels %llu walkers %llu output %llu "
                  "(count %llu radix %llu ties %llu collect %llu order %llu) clear %llu (spawn-prefix %llu) "
@@ -2443,7 +2355,7 @@ extern "C" int gw_topsim_kernel_attrs(gw_graph* g, int32_t* vgprs, int32_t* scra
   const gw_topsim_ws& t = g->ts;
   if (t.blocks == 0) return gw_fail(g, GW_ERR_STATE, "no TopSim workspace (call gw_topsim_prepare)");
   GW_GUARD_DEVICE(g, g->device);
-  const void* fn = kernel_fn(t.step, t.lds_row, t.pipe != 0, t.lds_bytes);
+  const void* fn = ts_kernel(t.step, t.lds_row, t.pipe != 0, t.lds_bytes).fn;
   if (!fn) return gw_fail(g, GW_ERR_STATE, "no TopSim kernel for step %d", t.step);
   hipFuncAttributes fa;
   const hipError_t e = hipFuncGetAttributes(&fa, fn);
@@ -2478,12 +2390,12 @@ extern "C" int gw_topsim_host(gw_graph* g, int variant, int sample, int step, do
   double* d_rows = nullptr;
   int64_t* d_st = nullptr;
   int rc = GW_OK;
-  if ((rc = ws_alloc(g, &d_src, chunk)) || (rc = ws_alloc(g, &d_st, 4)) ||
-      (out_rows ? (rc = ws_alloc(g, &d_rows, chunk * n)) : ((rc = ws_alloc(g, &d_ids, chunk * (int64_t)std::max(topk, 1))) ||
-                                                            (rc = ws_alloc(g, &d_sc, chunk * (int64_t)std::max(topk, 1)))))) {
-    ws_free(d_src); ws_free(d_st); ws_free(d_rows); ws_free(d_ids); ws_free(d_sc);
+  gw_dev_scratch scratch(g);
+  if ((rc = scratch.alloc(&d_src, chunk)) || (rc = scratch.alloc(&d_st, 4)) ||
+      (out_rows ? (rc = scratch.alloc(&d_rows, chunk * n))
+                : ((rc = scratch.alloc(&d_ids, chunk * (int64_t)std::max(topk, 1))) ||
+                   (rc = scratch.alloc(&d_sc, chunk * (int64_t)std::max(topk, 1))))))
     return rc;
-  }
   hipError_t e = hipMemset(d_st, 0, 4 * sizeof(int64_t));
   for (int64_t c0 = 0; c0 < nsrc && rc == GW_OK && e == hipSuccess; c0 += chunk) {
     const int64_t cn = std::min(chunk, nsrc - c0);
@@ -2500,7 +2412,6 @@ extern "C" int gw_topsim_host(gw_graph* g, int variant, int sample, int step, do
     }
   }
   if (rc == GW_OK && e == hipSuccess && stats) e = hipMemcpy(stats, d_st, 4 * sizeof(int64_t), hipMemcpyDeviceToHost);
-  ws_free(d_src); ws_free(d_st); ws_free(d_rows); ws_free(d_ids); ws_free(d_sc);
   if (rc != GW_OK) return rc;
   if (e != hipSuccess) return gw_fail(g, GW_ERR_DEVICE, "%s", hipGetErrorString(e));
   return GW_OK;
@@ -2532,15 +2443,11 @@ extern "C" int gw_topsim_write_text(gw_graph* g, int variant, int sample, int st
   int32_t *d_src = nullptr, *d_len = nullptr, *d_ids = nullptr;
   int64_t *d_begin = nullptr, *d_used = nullptr, *d_st = nullptr;
   double* d_sc = nullptr;
-  auto release = [&]() {
-    ws_free(d_src); ws_free(d_len); ws_free(d_ids); ws_free(d_begin); ws_free(d_used); ws_free(d_st); ws_free(d_sc);
-  };
-  if ((rc = ws_alloc(g, &d_src, chunk)) || (rc = ws_alloc(g, &d_len, chunk)) || (rc = ws_alloc(g, &d_begin, chunk)) ||
-      (rc = ws_alloc(g, &d_used, 1)) || (rc = ws_alloc(g, &d_st, 4)) || (rc = ws_alloc(g, &d_ids, cap)) ||
-      (rc = ws_alloc(g, &d_sc, cap))) {
-    release();
+  gw_dev_scratch scratch(g);
+  if ((rc = scratch.alloc(&d_src, chunk)) || (rc = scratch.alloc(&d_len, chunk)) ||
+      (rc = scratch.alloc(&d_begin, chunk)) || (rc = scratch.alloc(&d_used, 1)) || (rc = scratch.alloc(&d_st, 4)) ||
+      (rc = scratch.alloc(&d_ids, cap)) || (rc = scratch.alloc(&d_sc, cap)))
     return rc;
-  }
   int64_t tot_st[4] = {0, 0, 0, 0};
   std::vector<int64_t> h_begin;
   std::vector<int32_t> h_len, h_ids;
@@ -2563,9 +2470,9 @@ extern "C" int gw_topsim_write_text(gw_graph* g, int variant, int sample, int st
     if ((e = hipMemcpy(&used, d_used, sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
     if (rc == GW_ERR_CAPACITY && used > cap) {  // the rows need more room: grow and redo this batch
       cap = used + used / 8;
-      ws_free(d_ids);
-      ws_free(d_sc);
-      if ((rc = ws_alloc(g, &d_ids, cap)) || (rc = ws_alloc(g, &d_sc, cap))) break;
+      scratch.free(d_ids);
+      scratch.free(d_sc);
+      if ((rc = scratch.alloc(&d_ids, cap)) || (rc = scratch.alloc(&d_sc, cap))) break;
       continue;
     }
     if (rc != GW_OK) break;
@@ -2592,7 +2499,6 @@ extern "C" int gw_topsim_write_text(gw_graph* g, int variant, int sample, int st
     }
     c0 += cn;
   }
-  release();
   if (rc != GW_OK) return rc;
   if (e != hipSuccess) return gw_fail(g, GW_ERR_DEVICE, "%s", hipGetErrorString(e));
   if (stats)

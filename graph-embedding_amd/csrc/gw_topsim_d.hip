@@ -43,44 +43,6 @@ namespace {
 constexpr int TD_BLOCK = 256;
 constexpr int TD_WAVES = TD_BLOCK / 64;
 
-__device__ __forceinline__ int td_excl_scan(int v, int* s_wave, int* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_wave[wid] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int acc = 0;
-    for (int w = 0; w < TD_WAVES; ++w) {
-      int t = s_wave[w];
-      s_wave[w] = acc;
-      acc += t;
-    }
-    s_wave[TD_WAVES] = acc;
-  }
-  __syncthreads();
-  int r = s_wave[wid] + x - v;
-  *total = s_wave[TD_WAVES];
-  __syncthreads();
-  return r;
-}
-
-__device__ __forceinline__ int td_upper_bound(const int32_t* a, int n, int x) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    int mid = (lo + hi) >> 1;
-    if (a[mid] <= x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
 struct LvArgs {
   gw_dev_graph G;
   double sampled;
@@ -159,8 +121,8 @@ __global__ void __launch_bounds__(TD_BLOCK) k_topsim_levels(LvArgs A) {
           }
         }
         int tc, tn;
-        const int ec = td_excl_scan(cnt, s_wave, &tc);
-        const int en = td_excl_scan(nwk, s_wave, &tn);
+        const int ec = block_excl_scan<TD_WAVES>(cnt, s_wave, &tc);
+        const int en = block_excl_scan<TD_WAVES>(nwk, s_wave, &tn);
         if (j < sz) {
           CO[j] = total_children + ec;
           NW[j] = total_new + en;
@@ -179,7 +141,7 @@ __global__ void __launch_bounds__(TD_BLOCK) k_topsim_levels(LvArgs A) {
       __syncthreads();
       if (s_abort) break;
       for (int c = tid; c < total_children; c += TD_BLOCK) {
-        const int j = td_upper_bound(CO, sz + 1, c) - 1;
+        const int j = upper_bound_i32(CO, sz + 1, c) - 1;
         const int32_t v = V[j];
         const int k = c - CO[j];
         const int number = CO[j + 1] - CO[j];
@@ -384,24 +346,7 @@ __global__ void k_drw_finish(int64_t n, double denom, double* __restrict__ sim) 
   }
 }
 
-template <typename T>
-int td_alloc(gw_graph* g, T** p, int64_t count) {
-  *p = nullptr;
-  if (count < 1) count = 1;
-  if (hipMalloc((void**)p, sizeof(T) * (size_t)count) != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    g->err = "double-walk workspace allocation failed";
-    return GW_ERR_NOMEM;
-  }
-  return GW_OK;
-}
-
-template <typename T>
-void td_free(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
+constexpr const char* kTdAllocFailed = "double-walk workspace allocation failed";
 
 template <int STEP>
 hipError_t launch_levels(const LvArgs& A, int blocks, hipStream_t s) {
@@ -436,37 +381,23 @@ int levels_run(gw_graph* g, int sample, int step, uint64_t seed, const int32_t* 
   A.out = out_dev;
   A.cap = cap;
   int rc;
-  if ((rc = td_alloc(g, &A.qv, blocks * cap)) || (rc = td_alloc(g, &A.qw, blocks * cap)) ||
-      (rc = td_alloc(g, &A.qm, blocks * cap)) || (rc = td_alloc(g, &A.nv, blocks * cap)) ||
-      (rc = td_alloc(g, &A.nwk, blocks * cap)) || (rc = td_alloc(g, &A.nm, blocks * cap)) ||
-      (rc = td_alloc(g, &A.co, blocks * (cap + 1))) || (rc = td_alloc(g, &A.nwo, blocks * (cap + 1))) ||
-      (rc = td_alloc(g, &A.pos, blocks * n)) || (rc = td_alloc(g, &A.counter, 1)) ||
-      (rc = td_alloc(g, &A.error_flag, 1))) {
-    td_free(A.qv); td_free(A.qw); td_free(A.qm); td_free(A.nv); td_free(A.nwk); td_free(A.nm);
-    td_free(A.co); td_free(A.nwo); td_free(A.pos); td_free(A.counter); td_free(A.error_flag);
+  gw_dev_scratch scratch(g, kTdAllocFailed);
+  if ((rc = scratch.alloc(&A.qv, blocks * cap)) || (rc = scratch.alloc(&A.qw, blocks * cap)) ||
+      (rc = scratch.alloc(&A.qm, blocks * cap)) || (rc = scratch.alloc(&A.nv, blocks * cap)) ||
+      (rc = scratch.alloc(&A.nwk, blocks * cap)) || (rc = scratch.alloc(&A.nm, blocks * cap)) ||
+      (rc = scratch.alloc(&A.co, blocks * (cap + 1))) || (rc = scratch.alloc(&A.nwo, blocks * (cap + 1))) ||
+      (rc = scratch.alloc(&A.pos, blocks * n)) || (rc = scratch.alloc(&A.counter, 1)) ||
+      (rc = scratch.alloc(&A.error_flag, 1)))
     return rc;
-  }
   hipError_t e = hipMemsetAsync(out_dev, 0, sizeof(double) * (size_t)(ntask * step * n), s);
   if (e == hipSuccess) e = hipMemsetAsync(A.pos, 0xFF, sizeof(int32_t) * (size_t)(blocks * n), s);
   if (e == hipSuccess) e = hipMemsetAsync(A.counter, 0, sizeof(unsigned int), s);
   if (e == hipSuccess) e = hipMemsetAsync(A.error_flag, 0, sizeof(int), s);
-  if (e == hipSuccess) {
-    switch (step) {
-      case 1: e = launch_levels<1>(A, (int)blocks, s); break;
-      case 2: e = launch_levels<2>(A, (int)blocks, s); break;
-      case 3: e = launch_levels<3>(A, (int)blocks, s); break;
-      case 4: e = launch_levels<4>(A, (int)blocks, s); break;
-      case 5: e = launch_levels<5>(A, (int)blocks, s); break;
-      case 6: e = launch_levels<6>(A, (int)blocks, s); break;
-      case 7: e = launch_levels<7>(A, (int)blocks, s); break;
-      default: e = launch_levels<8>(A, (int)blocks, s); break;
-    }
-  }
+  if (e == hipSuccess)
+    e = gw_with_step(step, [&](auto S) { return launch_levels<decltype(S)::value>(A, (int)blocks, s); });
   int flag = 0;
   if (e == hipSuccess) e = hipMemcpyAsync(&flag, A.error_flag, sizeof(int), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  td_free(A.qv); td_free(A.qw); td_free(A.qm); td_free(A.nv); td_free(A.nwk); td_free(A.nm);
-  td_free(A.co); td_free(A.nwo); td_free(A.pos); td_free(A.counter); td_free(A.error_flag);
   GW_HIP_TRY(e);
   if (flag) {
     g->err = "double-walk sample(): a BFS level exceeded its queue capacity";
@@ -495,10 +426,10 @@ int check_common(gw_graph* g, int sample, int step) {
   return GW_OK;
 }
 
-int upload_cache(gw_graph* g, int step, double C, double** cache_dev) {
+int upload_cache(gw_graph* g, gw_dev_scratch& scratch, int step, double C, double** cache_dev) {
   std::vector<double> cache((size_t)step + 2, 0.0);
   for (int i = 0; i <= step; ++i) cache[(size_t)i] = std::pow(C, (double)i);  // Math.pow (:37)
-  int rc = td_alloc(g, cache_dev, step + 2);
+  int rc = scratch.alloc(cache_dev, step + 2);
   if (rc) return rc;
   GW_HIP_TRY(hipMemcpy(*cache_dev, cache.data(), sizeof(double) * (step + 2), hipMemcpyHostToDevice));
   return GW_OK;
@@ -525,13 +456,11 @@ int gw_dev_topsim_double(gw_graph* g, int sample, int step, double C, uint64_t s
       hti.push_back((int32_t)a);
       htj.push_back((int32_t)b);
     }
-  if ((rc = td_alloc(g, &M, n * step * n)) || (rc = td_alloc(g, &tv, n)) || (rc = td_alloc(g, &tc, n)) ||
-      (rc = td_alloc(g, &ti, (int64_t)hti.size())) || (rc = td_alloc(g, &tj, (int64_t)htj.size())) ||
-      (rc = upload_cache(g, step, C, &cache))) {
-    td_free(M); td_free(tv); td_free(tc); td_free(ti); td_free(tj); td_free(cache);
-    if (rc == GW_ERR_NOMEM) g->err = "TopSim_doubleSample needs STEP*n*n doubles of level rows";
+  gw_dev_scratch scratch(g, "TopSim_doubleSample needs STEP*n*n doubles of level rows");
+  if ((rc = scratch.alloc(&M, n * step * n)) || (rc = scratch.alloc(&tv, n)) || (rc = scratch.alloc(&tc, n)) ||
+      (rc = scratch.alloc(&ti, (int64_t)hti.size())) || (rc = scratch.alloc(&tj, (int64_t)htj.size())) ||
+      (rc = upload_cache(g, scratch, step, C, &cache)))
     return rc;
-  }
   hipError_t e = hipMemcpy(tv, hv.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(tc, 0, sizeof(int32_t) * n);
   if (e == hipSuccess) e = hipMemcpy(ti, hti.data(), sizeof(int32_t) * hti.size(), hipMemcpyHostToDevice);
@@ -544,7 +473,6 @@ int gw_dev_topsim_double(gw_graph* g, int sample, int step, double C, uint64_t s
       if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
   }
-  td_free(M); td_free(tv); td_free(tc); td_free(ti); td_free(tj); td_free(cache);
   if (rc != GW_OK) return rc;
   GW_HIP_TRY(e);
   return GW_OK;
@@ -578,12 +506,11 @@ int gw_dev_topsim_dev(gw_graph* g, int sample_total, int step, int topK, int sin
   double* cache = nullptr;
   int32_t *tv = nullptr, *tc = nullptr, *ps = nullptr, *pa = nullptr, *pb = nullptr, *pd = nullptr;
   const int64_t maxt = bsrc * (1 + topK);
-  if ((rc = td_alloc(g, &M, maxt * step * n)) || (rc = td_alloc(g, &tv, maxt)) || (rc = td_alloc(g, &tc, maxt)) ||
-      (rc = td_alloc(g, &ps, maxt)) || (rc = td_alloc(g, &pa, maxt)) || (rc = td_alloc(g, &pb, maxt)) ||
-      (rc = td_alloc(g, &pd, maxt)) || (rc = upload_cache(g, step, C, &cache))) {
-    td_free(M); td_free(tv); td_free(tc); td_free(ps); td_free(pa); td_free(pb); td_free(pd); td_free(cache);
+  gw_dev_scratch scratch(g, kTdAllocFailed);
+  if ((rc = scratch.alloc(&M, maxt * step * n)) || (rc = scratch.alloc(&tv, maxt)) || (rc = scratch.alloc(&tc, maxt)) ||
+      (rc = scratch.alloc(&ps, maxt)) || (rc = scratch.alloc(&pa, maxt)) || (rc = scratch.alloc(&pb, maxt)) ||
+      (rc = scratch.alloc(&pd, maxt)) || (rc = upload_cache(g, scratch, step, C, &cache)))
     return rc;
-  }
   hipError_t e = hipSuccess;
   for (int64_t i0 = 0; i0 < n && rc == GW_OK && e == hipSuccess; i0 += bsrc) {
     const int64_t i1 = std::min(n, i0 + bsrc);
@@ -619,7 +546,6 @@ int gw_dev_topsim_dev(gw_graph* g, int sample_total, int step, int topK, int sin
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
   }
-  td_free(M); td_free(tv); td_free(tc); td_free(ps); td_free(pa); td_free(pb); td_free(pd); td_free(cache);
   if (rc != GW_OK) return rc;
   GW_HIP_TRY(e);
   return GW_OK;
@@ -645,15 +571,14 @@ int gw_dev_double_random_walk(gw_graph* g, int sample, int step, double C, uint6
   }
   int32_t *paths = nullptr, *val = nullptr, *sval = nullptr;
   uint32_t *key = nullptr, *skey = nullptr;
-  void* tmp = nullptr;
+  char* tmp = nullptr;
   size_t tmpb = 0;
   GW_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmpb, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                                 (const int32_t*)nullptr, (int32_t*)nullptr, (int)nw, 0, 32, s));
-  if ((rc = td_alloc(g, &paths, nw * step)) || (rc = td_alloc(g, &key, nw)) || (rc = td_alloc(g, &skey, nw)) ||
-      (rc = td_alloc(g, &val, nw)) || (rc = td_alloc(g, &sval, nw)) || (rc = td_alloc(g, (char**)&tmp, (int64_t)tmpb))) {
-    td_free(paths); td_free(key); td_free(skey); td_free(val); td_free(sval); td_free(tmp);
+  gw_dev_scratch scratch(g, kTdAllocFailed);
+  if ((rc = scratch.alloc(&paths, nw * step)) || (rc = scratch.alloc(&key, nw)) || (rc = scratch.alloc(&skey, nw)) ||
+      (rc = scratch.alloc(&val, nw)) || (rc = scratch.alloc(&sval, nw)) || (rc = scratch.alloc(&tmp, (int64_t)tmpb)))
     return rc;
-  }
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ GW_TAG_TOPSIM;
   hipError_t e = hipMemsetAsync(sim_dev, 0, sizeof(double) * (size_t)(n * n), s);
   const unsigned gb = (unsigned)((nw + 255) / 256);
@@ -679,7 +604,6 @@ int gw_dev_double_random_walk(gw_graph* g, int sample, int step, double C, uint6
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  td_free(paths); td_free(key); td_free(skey); td_free(val); td_free(sval); td_free(tmp);
   GW_HIP_TRY(e);
   return GW_OK;
 }
@@ -695,13 +619,11 @@ extern "C" int gw_double_sim_host(gw_graph* g, int kind, int sample, int step, i
   if (n == 0) return GW_OK;
   double* d_sim = nullptr;
   int32_t* d_cand = nullptr;
-  if (hipMalloc((void**)&d_sim, sizeof(double) * (size_t)(n * n)) != hipSuccess) {
-    (void)hipGetLastError();
-    return gw_fail(g, GW_ERR_NOMEM, "n*n result does not fit in device memory");
-  }
+  gw_dev_scratch scratch(g);
+  if (scratch.alloc(&d_sim, n * n)) return gw_fail(g, GW_ERR_NOMEM, "n*n result does not fit in device memory");
   int rc = GW_OK;
   if (kind == GW_DOUBLE_DEV && topK > 0) {
-    if (hipMalloc((void**)&d_cand, sizeof(int32_t) * (size_t)(n * topK)) != hipSuccess ||
+    if (scratch.alloc(&d_cand, n * topK) ||
         hipMemcpy(d_cand, cand, sizeof(int32_t) * (size_t)(n * topK), hipMemcpyHostToDevice) != hipSuccess)
       rc = gw_fail(g, GW_ERR_DEVICE, "candidate upload failed");
   }
@@ -717,8 +639,6 @@ extern "C" int gw_double_sim_host(gw_graph* g, int kind, int sample, int step, i
   }
   if (rc == GW_OK && hipMemcpy(sim, d_sim, sizeof(double) * (size_t)(n * n), hipMemcpyDeviceToHost) != hipSuccess)
     rc = gw_fail(g, GW_ERR_DEVICE, "result copy failed");
-  if (d_sim) (void)hipFree(d_sim);
-  if (d_cand) (void)hipFree(d_cand);
   return rc;
 }
 

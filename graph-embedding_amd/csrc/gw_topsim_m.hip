@@ -64,44 +64,6 @@ struct TmArgs {
   int* error_flag;
 };
 
-__device__ __forceinline__ int tm_excl_scan(int v, int* s_wave, int* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_wave[wid] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int acc = 0;
-    for (int w = 0; w < TM_WAVES; ++w) {
-      int t = s_wave[w];
-      s_wave[w] = acc;
-      acc += t;
-    }
-    s_wave[TM_WAVES] = acc;
-  }
-  __syncthreads();
-  int r = s_wave[wid] + x - v;
-  *total = s_wave[TM_WAVES];
-  __syncthreads();
-  return r;
-}
-
-__device__ __forceinline__ int tm_upper_bound(const int32_t* a, int n, int x) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    int mid = (lo + hi) >> 1;
-    if (a[mid] <= x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
 // ---- FixedCacheMap in LDS, single lane (FixedCacheMap.java) -----------------
 struct Fcm {
   int N, NMAX, hmask;
@@ -359,8 +321,8 @@ __global__ void __launch_bounds__(TM_BLOCK) k_topsim_m(TmArgs A) {
             }
           }
           int tc, tn;
-          const int ec = tm_excl_scan(cnt, s_wave, &tc);
-          const int en = tm_excl_scan(nwk, s_wave, &tn);
+          const int ec = block_excl_scan<TM_WAVES>(cnt, s_wave, &tc);
+          const int en = block_excl_scan<TM_WAVES>(nwk, s_wave, &tn);
           if (j < sz) {
             CO[j] = total_children + ec;
             NW[j] = total_new + en;
@@ -383,7 +345,7 @@ __global__ void __launch_bounds__(TM_BLOCK) k_topsim_m(TmArgs A) {
         int32_t* Wn = W + (int64_t)(l + 1) * cap;
         double* Mn = M + (int64_t)((l + 1) & 1) * cap;
         for (int c = tid; c < total_children; c += TM_BLOCK) {
-          const int j = tm_upper_bound(CO, sz + 1, c) - 1;
+          const int j = upper_bound_i32(CO, sz + 1, c) - 1;
           const int32_t v = Vl[j];
           const int k = c - CO[j];
           const int number = CO[j + 1] - CO[j];
@@ -465,24 +427,7 @@ hipError_t launch_m(const TmArgs& A, int blocks, size_t lds, size_t lds_limit, i
   return hipGetLastError();
 }
 
-template <typename T>
-int tm_alloc(gw_graph* g, T** p, int64_t count) {
-  *p = nullptr;
-  if (count < 1) count = 1;
-  if (hipMalloc((void**)p, sizeof(T) * (size_t)count) != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    g->err = "TopSim_M workspace allocation failed";
-    return GW_ERR_NOMEM;
-  }
-  return GW_OK;
-}
-
-template <typename T>
-void tm_free(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
+constexpr const char* kTmAllocFailed = "TopSim_M workspace allocation failed";
 
 }  // namespace
 
@@ -556,35 +501,23 @@ int gw_dev_topsim_m(gw_graph* g, int variant, int capacity, int sample, int step
   int rc = GW_OK;
   const bool q = variant != GW_TOPSIM_SINGLE_RW;
   const int64_t lv = q ? blocks * (L + 1) * cap : 1;
-  if ((rc = tm_alloc(g, &A.qv, lv)) || (rc = tm_alloc(g, &A.qp, lv)) || (rc = tm_alloc(g, &A.qw, lv)) ||
-      (rc = tm_alloc(g, &A.qm, q ? blocks * 2 * cap : 1)) || (rc = tm_alloc(g, &A.co, q ? blocks * (cap + 1) : 1)) ||
-      (rc = tm_alloc(g, &A.nw, q ? blocks * (cap + 1) : 1)) || (rc = tm_alloc(g, &A.uk, blocks * cap)) ||
-      (rc = tm_alloc(g, &A.uvv, blocks * cap)) || (rc = tm_alloc(g, &A.src_counter, 1)) ||
-      (rc = tm_alloc(g, &A.error_flag, 1))) {
-    tm_free(A.qv); tm_free(A.qp); tm_free(A.qw); tm_free(A.qm); tm_free(A.co); tm_free(A.nw);
-    tm_free(A.uk); tm_free(A.uvv); tm_free(A.src_counter); tm_free(A.error_flag);
+  gw_dev_scratch scratch(g, kTmAllocFailed);
+  if ((rc = scratch.alloc(&A.qv, lv)) || (rc = scratch.alloc(&A.qp, lv)) || (rc = scratch.alloc(&A.qw, lv)) ||
+      (rc = scratch.alloc(&A.qm, q ? blocks * 2 * cap : 1)) || (rc = scratch.alloc(&A.co, q ? blocks * (cap + 1) : 1)) ||
+      (rc = scratch.alloc(&A.nw, q ? blocks * (cap + 1) : 1)) || (rc = scratch.alloc(&A.uk, blocks * cap)) ||
+      (rc = scratch.alloc(&A.uvv, blocks * cap)) || (rc = scratch.alloc(&A.src_counter, 1)) ||
+      (rc = scratch.alloc(&A.error_flag, 1)))
     return rc;
-  }
   hipError_t e = hipMemsetAsync(A.src_counter, 0, sizeof(unsigned int), s);
   if (e == hipSuccess) e = hipMemsetAsync(A.error_flag, 0, sizeof(int), s);
   int over = 0;
-  if (e == hipSuccess) {
-    switch (step) {
-      case 1: e = launch_m<1>(A, (int)blocks, lds, lds_limit, &over, s); break;
-      case 2: e = launch_m<2>(A, (int)blocks, lds, lds_limit, &over, s); break;
-      case 3: e = launch_m<3>(A, (int)blocks, lds, lds_limit, &over, s); break;
-      case 4: e = launch_m<4>(A, (int)blocks, lds, lds_limit, &over, s); break;
-      case 5: e = launch_m<5>(A, (int)blocks, lds, lds_limit, &over, s); break;
-      case 6: e = launch_m<6>(A, (int)blocks, lds, lds_limit, &over, s); break;
-      case 7: e = launch_m<7>(A, (int)blocks, lds, lds_limit, &over, s); break;
-      default: e = launch_m<8>(A, (int)blocks, lds, lds_limit, &over, s); break;
-    }
-  }
+  if (e == hipSuccess)
+    e = gw_with_step(step, [&](auto S) {
+      return launch_m<decltype(S)::value>(A, (int)blocks, lds, lds_limit, &over, s);
+    });
   int flag = 0;
   if (e == hipSuccess) e = hipMemcpyAsync(&flag, A.error_flag, sizeof(int), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  tm_free(A.qv); tm_free(A.qp); tm_free(A.qw); tm_free(A.qm); tm_free(A.co); tm_free(A.nw);
-  tm_free(A.uk); tm_free(A.uvv); tm_free(A.src_counter); tm_free(A.error_flag);
   GW_HIP_TRY(e);
   if (over) {
     g->err = "FixedCacheMap capacity does not fit the device's LDS (map and key index are LDS-resident)";
@@ -613,12 +546,11 @@ extern "C" int gw_topsim_m_host(gw_graph* g, int variant, int capacity, int samp
   float* d_v = nullptr;
   int64_t* d_st = nullptr;
   int rc;
-  if ((rc = tm_alloc(g, &d_src, nsrc)) || (rc = tm_alloc(g, &d_k, nsrc * (int64_t)capacity)) ||
-      (rc = tm_alloc(g, &d_v, nsrc * (int64_t)capacity)) || (rc = tm_alloc(g, &d_sz, nsrc)) ||
-      (rc = tm_alloc(g, &d_st, 4))) {
-    tm_free(d_src); tm_free(d_k); tm_free(d_v); tm_free(d_sz); tm_free(d_st);
+  gw_dev_scratch scratch(g, kTmAllocFailed);
+  if ((rc = scratch.alloc(&d_src, nsrc)) || (rc = scratch.alloc(&d_k, nsrc * (int64_t)capacity)) ||
+      (rc = scratch.alloc(&d_v, nsrc * (int64_t)capacity)) || (rc = scratch.alloc(&d_sz, nsrc)) ||
+      (rc = scratch.alloc(&d_st, 4)))
     return rc;
-  }
   hipError_t e = hipMemcpy(d_src, sources, nsrc * sizeof(int32_t), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(d_st, 0, 4 * sizeof(int64_t));
   if (e == hipSuccess) {
@@ -630,7 +562,6 @@ extern "C" int gw_topsim_m_host(gw_graph* g, int variant, int capacity, int samp
       if (e == hipSuccess && stats) e = hipMemcpy(stats, d_st, 4 * sizeof(int64_t), hipMemcpyDeviceToHost);
     }
   }
-  tm_free(d_src); tm_free(d_k); tm_free(d_v); tm_free(d_sz); tm_free(d_st);
   if (rc != GW_OK) return rc;
   if (e != hipSuccess) return gw_fail(g, GW_ERR_DEVICE, "%s", hipGetErrorString(e));
   return GW_OK;
