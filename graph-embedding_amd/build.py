@@ -26,7 +26,8 @@ HIP_SRCS = ["gw_n2v.hip", "gw_n2v_bitset.hip", "gw_topsim.hip", "gw_simrank.hip"
 CXX_SRCS = ["gw_graph_host.cpp", "gw_capi.cpp", "gw_comm.cpp", "gw_sgns_host.cpp", "gw_deepsim_host.cpp",
             "gw_ovr_host.cpp"]
 HEADERS = ["gw_internal.h", "gw_philox.h", "gw_device_common.h", "gw_sgns_law.h", "gw_sgns_internal.h",
-           "gw_deepsim_law.h", "gw_deepsim_internal.h", "gw_ovr_law.h", "gw_ovr_internal.h"]
+           "gw_deepsim_law.h", "gw_deepsim_internal.h", "gw_ovr_law.h", "gw_ovr_internal.h",
+           "gw_trainer_fail.h", "gw_trainer_device.h"]
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",

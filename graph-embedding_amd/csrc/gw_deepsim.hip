@@ -20,7 +20,26 @@
 
 #include "gw_deepsim_internal.h"
 #include "gw_deepsim_law.h"
-#include "gw_device_common.h"
+#include "gw_trainer_device.h"
+
+// Device state of a gw_deepsim handle (device >= 0); the buffers are freed with it.
+struct gw_deepsim_dev {
+  gw_dev_buf<float> par[4], am[4], av[4];  // {w1, b1, w2, b2} and their Adam moments
+  gw_dev_buf<float> gw1;                   // [V][dim] gradient rows of w1, all 0 between steps
+  bool gw1_dirty = false;        // a call ended before its rows were zeroed again: the next call clears gw1
+  gw_dev_buf<float> gsmall;      // gb1 [dim]
+  gw_dev_buf<float> gw2;         // diagnostic [dim][V] + gb2 [V], allocated by gw_deepsim_gradients
+  gw_dev_buf<float> logits;      // [B][V]
+  gw_dev_buf<float> hidden;      // [B][dim] hidden, then [B][dim] pre-activation
+  gw_dev_buf<float> tmax, tsum;  // [ntiles][B] each
+  gw_dev_buf<float> rowM;        // [B] M, then [B] S
+  gw_dev_buf<float> part;        // [ntiles][B][dim]
+  gw_dev_buf<float> dh;          // [B][dim]
+  gw_dev_buf<int32_t> centre, tgt_id, tgt_n, tab_id, tab_cnt, elig_len;
+  gw_dev_buf<float> tgt_val, ysum, tab_val, tem;
+  gw_dev_buf<int64_t> labels, elig;
+  gw_dev_buf<double> loss;  // per-step losses of one train call
+};
 
 namespace {
 
@@ -458,25 +477,11 @@ __global__ void k_ds_zero_rows(const DsArgs A) {
   A.gw1[(int64_t)A.centre[blockIdx.x] * A.d + threadIdx.x] = 0.0f;
 }
 
-#define DS_TRY(expr)                                                                                        \
-  do {                                                                                                      \
-    hipError_t _e = (expr);                                                                                 \
-    if (_e != hipSuccess) return gw_deepsim_fail(m, GW_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
-
-#define DS_GUARD(m)                    \
-  gw_device_guard gw_dg_((m)->device); \
-  if (!gw_dg_.ok) return gw_deepsim_fail((m), GW_ERR_DEVICE, "cannot select HIP device %d", (m)->device)
-
-template <typename T>
-hipError_t dmalloc(T** p, size_t count) {
-  return hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-}
-
 size_t fwd_lds(const gw_deepsim* m) { return (size_t)m->p.batch * (kHsPitch + kLtPitch) * sizeof(float); }
 size_t bwd_lds(const gw_deepsim* m) { return ((size_t)m->p.batch * kTW + (size_t)kTW * m->p.dim) * sizeof(float); }
 
 DsArgs make_args(const gw_deepsim* m) {
+  const gw_deepsim_dev& dv = *m->dev;
   DsArgs A = {};
   A.V = m->V;
   A.B = m->p.batch;
@@ -489,42 +494,43 @@ DsArgs make_args(const gw_deepsim* m) {
   A.seed = m->p.seed;
   A.walks = m->walks;
   A.walk_len = m->walk_len;
-  A.labels = m->has_labels ? m->d_labels : nullptr;
+  A.labels = m->has_labels ? dv.labels.get() : nullptr;
   A.n_labels = (int64_t)m->labels.size();
-  A.elig = m->d_elig;
-  A.elig_len = m->d_elig_len;
+  A.elig = dv.elig.get();
+  A.elig_len = dv.elig_len.get();
   A.n_elig = (int64_t)m->elig.size();
-  A.tab_id = m->d_tab_id;
-  A.tab_cnt = m->d_tab_cnt;
-  A.tab_val = m->d_tab_val;
-  A.tem = m->d_tem;
-  A.centre = m->d_centre;
-  A.tgt_id = m->d_tgt_id;
-  A.tgt_val = m->d_tgt_val;
-  A.tgt_n = m->d_tgt_n;
-  A.ysum = m->d_ysum;
-  A.w1 = m->d_par[0], A.b1 = m->d_par[1], A.w2 = m->d_par[2], A.b2 = m->d_par[3];
-  A.m1 = m->d_am[0], A.mb1 = m->d_am[1], A.m2 = m->d_am[2], A.mb2 = m->d_am[3];
-  A.v1 = m->d_av[0], A.vb1 = m->d_av[1], A.v2 = m->d_av[2], A.vb2 = m->d_av[3];
-  A.gw1 = m->d_gw1;
-  A.gb1 = m->d_gsmall;
-  A.gw2 = m->d_gw2;
-  A.logits = m->d_logits;
-  A.hidden = m->d_hidden;
-  A.tmax = m->d_tmax;
-  A.tsum = m->d_tsum;
-  A.rowM = m->d_rowM;
-  A.part = m->d_part;
-  A.dh = m->d_dh;
+  A.tab_id = dv.tab_id.get();
+  A.tab_cnt = dv.tab_cnt.get();
+  A.tab_val = dv.tab_val.get();
+  A.tem = dv.tem.get();
+  A.centre = dv.centre.get();
+  A.tgt_id = dv.tgt_id.get();
+  A.tgt_val = dv.tgt_val.get();
+  A.tgt_n = dv.tgt_n.get();
+  A.ysum = dv.ysum.get();
+  A.w1 = dv.par[0].get(), A.b1 = dv.par[1].get(), A.w2 = dv.par[2].get(), A.b2 = dv.par[3].get();
+  A.m1 = dv.am[0].get(), A.mb1 = dv.am[1].get(), A.m2 = dv.am[2].get(), A.mb2 = dv.am[3].get();
+  A.v1 = dv.av[0].get(), A.vb1 = dv.av[1].get(), A.v2 = dv.av[2].get(), A.vb2 = dv.av[3].get();
+  A.gw1 = dv.gw1.get();
+  A.gb1 = dv.gsmall.get();
+  A.gw2 = dv.gw2.get();
+  A.logits = dv.logits.get();
+  A.hidden = dv.hidden.get();
+  A.tmax = dv.tmax.get();
+  A.tsum = dv.tsum.get();
+  A.rowM = dv.rowM.get();
+  A.part = dv.part.get();
+  A.dh = dv.dh.get();
   return A;
 }
 
 // The w1 gradient buffer is all 0 between steps (k_ds_zero_rows ends every step).  A call that ended early
 // leaves gw1_dirty set; the next call clears the whole buffer before it launches anything.
 int clean_gw1(gw_deepsim* m, hipStream_t st) {
-  if (!m->gw1_dirty) return GW_OK;
-  DS_TRY(hipMemsetAsync(m->d_gw1, 0, (size_t)m->V * (size_t)m->p.dim * sizeof(float), st));
-  m->gw1_dirty = false;
+  gw_deepsim_dev& dv = *m->dev;
+  if (!dv.gw1_dirty) return GW_OK;
+  GW_DEV_TRY(m, hipMemsetAsync(dv.gw1.get(), 0, (size_t)m->V * (size_t)m->p.dim * sizeof(float), st));
+  dv.gw1_dirty = false;
   return GW_OK;
 }
 
@@ -543,130 +549,108 @@ int launch_step(gw_deepsim* m, const DsArgs& A, uint64_t t, int adam, double* lo
     k_ds_adam_w1<<<(unsigned)((A.V * d + 255) / 256), 256, 0, st>>>(A, C);
     k_ds_zero_rows<<<B, d, 0, st>>>(A);
   }
-  DS_TRY(hipGetLastError());
+  GW_DEV_TRY(m, hipGetLastError());
   return GW_OK;
 }
 
 }  // namespace
 
 int gw_ds_dev_alloc(gw_deepsim* m, const std::vector<float> init[4]) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return gw_deepsim_fail(m, GW_ERR_DEVICE, "no HIP device visible (device = -1 evaluates the law on the host)");
-  if (m->device >= count) return gw_deepsim_fail(m, GW_ERR_INVALID, "device ordinal out of range");
-  DS_GUARD(m);
-  const size_t B = (size_t)m->p.batch, d = (size_t)m->p.dim, V = (size_t)m->V, nt = (size_t)m->ntiles, W = (size_t)m->W;
+  const int rc = gw_trainer_open_device(m);
+  if (rc != GW_OK) return rc;
+  GW_DEV_GUARD(m);
+  gw_deepsim_dev& dv = *m->dev;
+  const int64_t B = m->p.batch, d = m->p.dim, V = m->V, nt = m->ntiles, W = m->W;
   hipError_t e = hipSuccess;
   for (int t = 0; t < 4 && e == hipSuccess; ++t) {
     const size_t n = gw_ds_numel(m, t);
-    e = dmalloc(&m->d_par[t], n);
-    if (e == hipSuccess) e = dmalloc(&m->d_am[t], n);
-    if (e == hipSuccess) e = dmalloc(&m->d_av[t], n);
-    if (e == hipSuccess) e = hipMemcpy(m->d_par[t], init[t].data(), n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(m->d_am[t], 0, n * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(m->d_av[t], 0, n * sizeof(float));
+    e = dv.par[t].alloc((int64_t)n);
+    if (e == hipSuccess) e = dv.am[t].alloc((int64_t)n);
+    if (e == hipSuccess) e = dv.av[t].alloc((int64_t)n);
+    if (e == hipSuccess) e = hipMemcpy(dv.par[t].get(), init[t].data(), n * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dv.am[t].get(), 0, n * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(dv.av[t].get(), 0, n * sizeof(float));
   }
-  if (e == hipSuccess) e = dmalloc(&m->d_gw1, V * d);
-  if (e == hipSuccess) e = hipMemset(m->d_gw1, 0, V * d * sizeof(float));
-  if (e == hipSuccess) e = dmalloc(&m->d_gsmall, d);
-  if (e == hipSuccess) e = dmalloc(&m->d_logits, B * V);
-  if (e == hipSuccess) e = dmalloc(&m->d_hidden, 2 * B * d);
-  if (e == hipSuccess) e = dmalloc(&m->d_tmax, nt * B);
-  if (e == hipSuccess) e = dmalloc(&m->d_tsum, nt * B);
-  if (e == hipSuccess) e = dmalloc(&m->d_rowM, 2 * B);
-  if (e == hipSuccess) e = dmalloc(&m->d_part, nt * B * d);
-  if (e == hipSuccess) e = dmalloc(&m->d_dh, B * d);
-  if (e == hipSuccess) e = dmalloc(&m->d_centre, B);
-  if (e == hipSuccess) e = dmalloc(&m->d_tgt_id, B * W);
-  if (e == hipSuccess) e = dmalloc(&m->d_tgt_val, B * W);
-  if (e == hipSuccess) e = dmalloc(&m->d_tgt_n, B);
-  if (e == hipSuccess) e = dmalloc(&m->d_ysum, B);
-  if (e == hipSuccess) e = dmalloc(&m->d_tem, V);
-  if (e == hipSuccess) e = dmalloc(&m->d_tab_cnt, V);
+  if (e == hipSuccess) e = dv.gw1.alloc(V * d);
+  if (e == hipSuccess) e = hipMemset(dv.gw1.get(), 0, (size_t)(V * d) * sizeof(float));
+  if (e == hipSuccess) e = dv.gsmall.alloc(d);
+  if (e == hipSuccess) e = dv.logits.alloc(B * V);
+  if (e == hipSuccess) e = dv.hidden.alloc(2 * B * d);
+  if (e == hipSuccess) e = dv.tmax.alloc(nt * B);
+  if (e == hipSuccess) e = dv.tsum.alloc(nt * B);
+  if (e == hipSuccess) e = dv.rowM.alloc(2 * B);
+  if (e == hipSuccess) e = dv.part.alloc(nt * B * d);
+  if (e == hipSuccess) e = dv.dh.alloc(B * d);
+  if (e == hipSuccess) e = dv.centre.alloc(B);
+  if (e == hipSuccess) e = dv.tgt_id.alloc(B * W);
+  if (e == hipSuccess) e = dv.tgt_val.alloc(B * W);
+  if (e == hipSuccess) e = dv.tgt_n.alloc(B);
+  if (e == hipSuccess) e = dv.ysum.alloc(B);
+  if (e == hipSuccess) e = dv.tem.alloc(V);
+  if (e == hipSuccess) e = dv.tab_cnt.alloc(V);
   if (e != hipSuccess) return gw_deepsim_fail(m, GW_ERR_NOMEM, "device allocation failed: %s", hipGetErrorString(e));
   return GW_OK;
 }
 
 void gw_ds_dev_free(gw_deepsim* m) {
   gw_device_guard dg(m->device);
-  void* ps[] = {m->d_gw1,    m->d_gsmall, m->d_gw2,     m->d_logits,  m->d_hidden, m->d_tmax,   m->d_tsum,
-                m->d_rowM,   m->d_part,   m->d_dh,      m->d_centre,  m->d_tgt_id, m->d_tgt_val, m->d_tgt_n,
-                m->d_ysum,   m->d_tab_id, m->d_tab_cnt, m->d_tab_val, m->d_tem,    m->d_labels, m->d_elig,
-                m->d_elig_len, m->d_loss};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  for (int t = 0; t < 4; ++t) {
-    if (m->d_par[t]) (void)hipFree(m->d_par[t]);
-    if (m->d_am[t]) (void)hipFree(m->d_am[t]);
-    if (m->d_av[t]) (void)hipFree(m->d_av[t]);
-    m->d_par[t] = m->d_am[t] = m->d_av[t] = nullptr;
-  }
-  m->d_gw1 = m->d_gsmall = m->d_gw2 = m->d_logits = m->d_hidden = m->d_tmax = m->d_tsum = nullptr;
-  m->d_rowM = m->d_part = m->d_dh = m->d_tgt_val = m->d_ysum = m->d_tab_val = m->d_tem = nullptr;
-  m->d_centre = m->d_tgt_id = m->d_tgt_n = m->d_tab_id = m->d_tab_cnt = m->d_elig_len = nullptr;
-  m->d_labels = m->d_elig = nullptr;
-  m->d_loss = nullptr;
+  delete m->dev;
+  m->dev = nullptr;
 }
 
 int gw_ds_dev_fetch_table(gw_deepsim* m, const int32_t* ids_dev, const double* scores_dev, int topk,
                           std::vector<int32_t>* ids, std::vector<double>* scores) {
-  DS_GUARD(m);
+  GW_DEV_GUARD(m);
   const size_t n = (size_t)m->V * (size_t)topk;
   ids->resize(n);
   scores->resize(n);
-  DS_TRY(hipDeviceSynchronize());  // the producer (gw_topsim on any stream) is complete
-  DS_TRY(hipMemcpy(ids->data(), ids_dev, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  DS_TRY(hipMemcpy(scores->data(), scores_dev, n * sizeof(double), hipMemcpyDeviceToHost));
+  GW_DEV_TRY(m, hipDeviceSynchronize());  // the producer (gw_topsim on any stream) is complete
+  GW_DEV_TRY(m, hipMemcpy(ids->data(), ids_dev, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  GW_DEV_TRY(m, hipMemcpy(scores->data(), scores_dev, n * sizeof(double), hipMemcpyDeviceToHost));
   return GW_OK;
 }
 
 int gw_ds_dev_upload_table(gw_deepsim* m) {
-  DS_GUARD(m);
+  GW_DEV_GUARD(m);
+  gw_deepsim_dev& dv = *m->dev;
   const size_t n = (size_t)m->V * (size_t)m->topk;
-  if (m->d_tab_id) (void)hipFree(m->d_tab_id);
-  if (m->d_tab_val) (void)hipFree(m->d_tab_val);
-  m->d_tab_id = nullptr;
-  m->d_tab_val = nullptr;
-  hipError_t e = dmalloc(&m->d_tab_id, n);
-  if (e == hipSuccess) e = dmalloc(&m->d_tab_val, n);
+  hipError_t e = dv.tab_id.alloc((int64_t)n);
+  if (e == hipSuccess) e = dv.tab_val.alloc((int64_t)n);
   if (e != hipSuccess) return gw_deepsim_fail(m, GW_ERR_NOMEM, "device allocation failed: %s", hipGetErrorString(e));
-  DS_TRY(hipMemcpy(m->d_tab_id, m->tab_id.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-  DS_TRY(hipMemcpy(m->d_tab_val, m->tab_val.data(), n * sizeof(float), hipMemcpyHostToDevice));
-  DS_TRY(hipMemcpy(m->d_tab_cnt, m->tab_cnt.data(), (size_t)m->V * sizeof(int32_t), hipMemcpyHostToDevice));
-  DS_TRY(hipMemcpy(m->d_tem, m->tem.data(), (size_t)m->V * sizeof(float), hipMemcpyHostToDevice));
+  GW_DEV_TRY(m, hipMemcpy(dv.tab_id.get(), m->tab_id.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+  GW_DEV_TRY(m, hipMemcpy(dv.tab_val.get(), m->tab_val.data(), n * sizeof(float), hipMemcpyHostToDevice));
+  GW_DEV_TRY(m, hipMemcpy(dv.tab_cnt.get(), m->tab_cnt.data(), (size_t)m->V * sizeof(int32_t), hipMemcpyHostToDevice));
+  GW_DEV_TRY(m, hipMemcpy(dv.tem.get(), m->tem.data(), (size_t)m->V * sizeof(float), hipMemcpyHostToDevice));
   return GW_OK;
 }
 
 int gw_ds_dev_scan_walks(gw_deepsim* m, std::vector<int32_t>* len) {
-  DS_GUARD(m);
-  if (m->d_labels) (void)hipFree(m->d_labels);
-  m->d_labels = nullptr;
+  GW_DEV_GUARD(m);
+  gw_deepsim_dev& dv = *m->dev;
+  dv.labels.reset();
   if (m->has_labels) {
-    if (dmalloc(&m->d_labels, m->labels.size()) != hipSuccess)
-      return gw_deepsim_fail(m, GW_ERR_NOMEM, "device allocation failed");
-    DS_TRY(hipMemcpy(m->d_labels, m->labels.data(), m->labels.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    const size_t n = m->labels.size();
+    if (dv.labels.alloc((int64_t)n) != hipSuccess) return gw_deepsim_fail(m, GW_ERR_NOMEM, "device allocation failed");
+    GW_DEV_TRY(m, hipMemcpy(dv.labels.get(), m->labels.data(), n * sizeof(int64_t), hipMemcpyHostToDevice));
   }
   if (m->nwalks == 0) return GW_OK;
   const int64_t blocks = (m->nwalks + 255) / 256;
   if (blocks > 0x7FFFFFFF) return gw_deepsim_fail(m, GW_ERR_UNSUPPORTED, "too many walks for one launch");
-  int32_t* d_len = nullptr;
-  unsigned long long* d_flag = nullptr;
-  if (dmalloc(&d_len, (size_t)m->nwalks) != hipSuccess || dmalloc(&d_flag, 1) != hipSuccess) {
-    if (d_len) (void)hipFree(d_len);
+  gw_dev_buf<int32_t> d_len;
+  gw_dev_buf<unsigned long long> d_flag;
+  if (d_len.alloc(m->nwalks) != hipSuccess || d_flag.alloc(1) != hipSuccess)
     return gw_deepsim_fail(m, GW_ERR_NOMEM, "device allocation failed");
-  }
   unsigned long long bad = 0;
   hipError_t e = hipDeviceSynchronize();  // the walks' producer is complete
-  if (e == hipSuccess) e = hipMemset(d_flag, 0, sizeof bad);
+  if (e == hipSuccess) e = hipMemset(d_flag.get(), 0, sizeof bad);
   if (e == hipSuccess) {
-    k_ds_scan<<<(unsigned)blocks, 256>>>(m->walks, m->nwalks, m->walk_len, m->d_labels, (int64_t)m->labels.size(), m->V,
-                                         d_len, d_flag);
+    k_ds_scan<<<(unsigned)blocks, 256>>>(m->walks, m->nwalks, m->walk_len, dv.labels.get(), (int64_t)m->labels.size(),
+                                         m->V, d_len.get(), d_flag.get());
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpy(&bad, d_flag, sizeof bad, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(len->data(), d_len, (size_t)m->nwalks * sizeof(int32_t), hipMemcpyDeviceToHost);
-  (void)hipFree(d_len);
-  (void)hipFree(d_flag);
+  if (e == hipSuccess) e = hipMemcpy(&bad, d_flag.get(), sizeof bad, hipMemcpyDeviceToHost);
+  if (e == hipSuccess)
+    e = hipMemcpy(len->data(), d_len.get(), (size_t)m->nwalks * sizeof(int32_t), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return gw_deepsim_fail(m, GW_ERR_DEVICE, "walk scan: %s", hipGetErrorString(e));
   if (bad)
     return gw_deepsim_fail(m, GW_ERR_RANGE, "walk %lld holds a token that maps outside [0, %lld)", (long long)bad - 1,
@@ -675,92 +659,87 @@ int gw_ds_dev_scan_walks(gw_deepsim* m, std::vector<int32_t>* len) {
 }
 
 int gw_ds_dev_upload_elig(gw_deepsim* m) {
-  DS_GUARD(m);
-  if (m->d_elig) (void)hipFree(m->d_elig);
-  if (m->d_elig_len) (void)hipFree(m->d_elig_len);
-  m->d_elig = nullptr;
-  m->d_elig_len = nullptr;
+  GW_DEV_GUARD(m);
+  gw_deepsim_dev& dv = *m->dev;
   const size_t n = m->elig.size();
-  if (dmalloc(&m->d_elig, n) != hipSuccess || dmalloc(&m->d_elig_len, n) != hipSuccess)
+  if (dv.elig.alloc((int64_t)n) != hipSuccess || dv.elig_len.alloc((int64_t)n) != hipSuccess)
     return gw_deepsim_fail(m, GW_ERR_NOMEM, "device allocation failed");
-  DS_TRY(hipMemcpy(m->d_elig, m->elig.data(), n * sizeof(int64_t), hipMemcpyHostToDevice));
-  DS_TRY(hipMemcpy(m->d_elig_len, m->elig_len.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+  GW_DEV_TRY(m, hipMemcpy(dv.elig.get(), m->elig.data(), n * sizeof(int64_t), hipMemcpyHostToDevice));
+  GW_DEV_TRY(m, hipMemcpy(dv.elig_len.get(), m->elig_len.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
   return GW_OK;
 }
 
 int gw_ds_dev_train(gw_deepsim* m, int64_t step_begin, int64_t step_count, double* loss_out, void* stream) {
-  DS_GUARD(m);
+  GW_DEV_GUARD(m);
+  gw_deepsim_dev& dv = *m->dev;
   hipStream_t st = (hipStream_t)stream;
-  if (loss_out && step_count > m->loss_cap) {
-    if (m->d_loss) (void)hipFree(m->d_loss);
-    m->d_loss = nullptr;
-    m->loss_cap = 0;
-    if (dmalloc(&m->d_loss, (size_t)step_count) != hipSuccess)
-      return gw_deepsim_fail(m, GW_ERR_NOMEM, "device allocation failed");
-    m->loss_cap = step_count;
-  }
+  if (loss_out && dv.loss.grow(step_count) != hipSuccess)
+    return gw_deepsim_fail(m, GW_ERR_NOMEM, "device allocation failed");
   const DsArgs A = make_args(m);
   int rc = clean_gw1(m, st);
   if (rc != GW_OK) return rc;
-  m->gw1_dirty = true;
+  dv.gw1_dirty = true;
   for (int64_t i = 0; i < step_count; ++i) {
-    rc = launch_step(m, A, (uint64_t)(step_begin + i), 1, loss_out ? m->d_loss + i : nullptr, st);
+    rc = launch_step(m, A, (uint64_t)(step_begin + i), 1, loss_out ? dv.loss.get() + i : nullptr, st);
     if (rc != GW_OK) return rc;
   }
-  if (loss_out)
-    DS_TRY(hipMemcpyAsync(loss_out, m->d_loss, (size_t)step_count * sizeof(double), hipMemcpyDeviceToHost, st));
-  DS_TRY(hipStreamSynchronize(st));
-  m->gw1_dirty = false;
+  const size_t loss_bytes = (size_t)step_count * sizeof(double);
+  if (loss_out) GW_DEV_TRY(m, hipMemcpyAsync(loss_out, dv.loss.get(), loss_bytes, hipMemcpyDeviceToHost, st));
+  GW_DEV_TRY(m, hipStreamSynchronize(st));
+  dv.gw1_dirty = false;
   return GW_OK;
 }
 
 int gw_ds_dev_gradients(gw_deepsim* m, int64_t step, float* gw1, float* gb1, float* gw2, float* gb2) {
-  DS_GUARD(m);
+  GW_DEV_GUARD(m);
+  gw_deepsim_dev& dv = *m->dev;
   const size_t V = (size_t)m->V, d = (size_t)m->p.dim;
-  if (!m->d_gw2 && dmalloc(&m->d_gw2, d * V + V) != hipSuccess)
+  if (dv.gw2.grow((int64_t)(d * V + V)) != hipSuccess)
     return gw_deepsim_fail(m, GW_ERR_NOMEM, "device allocation failed");
   const DsArgs A = make_args(m);
   int rc = clean_gw1(m, nullptr);
   if (rc != GW_OK) return rc;
-  m->gw1_dirty = true;  // until the rows this step writes are zero again, whichever way this call ends
+  dv.gw1_dirty = true;  // until the rows this step writes are zero again, whichever way this call ends
   rc = launch_step(m, A, (uint64_t)step, 0, nullptr, nullptr);
   if (rc != GW_OK) return rc;
-  DS_TRY(hipDeviceSynchronize());
-  if (gw1) DS_TRY(hipMemcpy(gw1, m->d_gw1, V * d * sizeof(float), hipMemcpyDeviceToHost));
-  if (gb1) DS_TRY(hipMemcpy(gb1, m->d_gsmall, d * sizeof(float), hipMemcpyDeviceToHost));
-  if (gw2) DS_TRY(hipMemcpy(gw2, m->d_gw2, d * V * sizeof(float), hipMemcpyDeviceToHost));
-  if (gb2) DS_TRY(hipMemcpy(gb2, m->d_gw2 + d * V, V * sizeof(float), hipMemcpyDeviceToHost));
+  GW_DEV_TRY(m, hipDeviceSynchronize());
+  if (gw1) GW_DEV_TRY(m, hipMemcpy(gw1, dv.gw1.get(), V * d * sizeof(float), hipMemcpyDeviceToHost));
+  if (gb1) GW_DEV_TRY(m, hipMemcpy(gb1, dv.gsmall.get(), d * sizeof(float), hipMemcpyDeviceToHost));
+  if (gw2) GW_DEV_TRY(m, hipMemcpy(gw2, dv.gw2.get(), d * V * sizeof(float), hipMemcpyDeviceToHost));
+  if (gb2) GW_DEV_TRY(m, hipMemcpy(gb2, dv.gw2.get() + d * V, V * sizeof(float), hipMemcpyDeviceToHost));
   k_ds_zero_rows<<<A.B, A.d>>>(A);
-  DS_TRY(hipGetLastError());
-  DS_TRY(hipDeviceSynchronize());
-  m->gw1_dirty = false;
+  GW_DEV_TRY(m, hipGetLastError());
+  GW_DEV_TRY(m, hipDeviceSynchronize());
+  dv.gw1_dirty = false;
   return GW_OK;
 }
 
 int gw_ds_dev_batch(gw_deepsim* m, int64_t step, int32_t* centre, int32_t* tgt_id, float* tgt_val, int32_t* tgt_n,
                     float* ysum) {
-  DS_GUARD(m);
+  GW_DEV_GUARD(m);
+  gw_deepsim_dev& dv = *m->dev;
   const DsArgs A = make_args(m);
   const size_t B = (size_t)A.B, W = (size_t)A.W;
   k_ds_batch<<<A.B, 64>>>(A, (uint64_t)step);
-  DS_TRY(hipGetLastError());
-  DS_TRY(hipDeviceSynchronize());
-  if (centre) DS_TRY(hipMemcpy(centre, m->d_centre, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (tgt_id) DS_TRY(hipMemcpy(tgt_id, m->d_tgt_id, B * W * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (tgt_val) DS_TRY(hipMemcpy(tgt_val, m->d_tgt_val, B * W * sizeof(float), hipMemcpyDeviceToHost));
-  if (tgt_n) DS_TRY(hipMemcpy(tgt_n, m->d_tgt_n, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (ysum) DS_TRY(hipMemcpy(ysum, m->d_ysum, B * sizeof(float), hipMemcpyDeviceToHost));
+  GW_DEV_TRY(m, hipGetLastError());
+  GW_DEV_TRY(m, hipDeviceSynchronize());
+  if (centre) GW_DEV_TRY(m, hipMemcpy(centre, dv.centre.get(), B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (tgt_id) GW_DEV_TRY(m, hipMemcpy(tgt_id, dv.tgt_id.get(), B * W * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (tgt_val) GW_DEV_TRY(m, hipMemcpy(tgt_val, dv.tgt_val.get(), B * W * sizeof(float), hipMemcpyDeviceToHost));
+  if (tgt_n) GW_DEV_TRY(m, hipMemcpy(tgt_n, dv.tgt_n.get(), B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (ysum) GW_DEV_TRY(m, hipMemcpy(ysum, dv.ysum.get(), B * sizeof(float), hipMemcpyDeviceToHost));
   return GW_OK;
 }
 
 int gw_ds_dev_export(gw_deepsim* m, float* const par[4], float* const am[4], float* const av[4]) {
-  DS_GUARD(m);
-  DS_TRY(hipDeviceSynchronize());
+  GW_DEV_GUARD(m);
+  gw_deepsim_dev& dv = *m->dev;
+  GW_DEV_TRY(m, hipDeviceSynchronize());
   for (int t = 0; t < 4; ++t) {
     const size_t bytes = gw_ds_numel(m, t) * sizeof(float);
-    if (par && par[t]) DS_TRY(hipMemcpy(par[t], m->d_par[t], bytes, hipMemcpyDeviceToHost));
-    if (am && am[t]) DS_TRY(hipMemcpy(am[t], m->d_am[t], bytes, hipMemcpyDeviceToHost));
-    if (av && av[t]) DS_TRY(hipMemcpy(av[t], m->d_av[t], bytes, hipMemcpyDeviceToHost));
+    if (par && par[t]) GW_DEV_TRY(m, hipMemcpy(par[t], dv.par[t].get(), bytes, hipMemcpyDeviceToHost));
+    if (am && am[t]) GW_DEV_TRY(m, hipMemcpy(am[t], dv.am[t].get(), bytes, hipMemcpyDeviceToHost));
+    if (av && av[t]) GW_DEV_TRY(m, hipMemcpy(av[t], dv.av[t].get(), bytes, hipMemcpyDeviceToHost));
   }
   return GW_OK;
 }
@@ -769,30 +748,18 @@ extern "C" int gw_deepsim_kernel_attrs(gw_deepsim* m, int cap, const char** name
                                        int32_t* scratch_bytes, int32_t* lds_bytes, int32_t* count) {
   if (!m) return gw_deepsim_fail(nullptr, GW_ERR_INVALID, "NULL handle");
   if (m->device < 0) return gw_deepsim_fail(m, GW_ERR_STATE, "host evaluation launches no kernel");
-  DS_GUARD(m);
-  struct K {
-    const char* name;
-    const void* fn;
-    size_t dyn;
-  };
-  const K ks[] = {{"k_ds_batch", (const void*)k_ds_batch, 0},
-                  {"k_ds_hidden", (const void*)k_ds_hidden, 0},
-                  {"k_ds_forward", (const void*)k_ds_forward, fwd_lds(m)},
-                  {"k_ds_rowstats", (const void*)k_ds_rowstats, 0},
-                  {"k_ds_backward", (const void*)k_ds_backward, bwd_lds(m)},
-                  {"k_ds_reduce_dh", (const void*)k_ds_reduce_dh, 0},
-                  {"k_ds_dw1", (const void*)k_ds_dw1, 0},
-                  {"k_ds_adam_w1", (const void*)k_ds_adam_w1, 0},
-                  {"k_ds_zero_rows", (const void*)k_ds_zero_rows, 0}};
-  const int n = (int)(sizeof ks / sizeof ks[0]);
-  if (count) *count = n;
-  for (int i = 0; i < n && i < cap; ++i) {
-    hipFuncAttributes fa;
-    DS_TRY(hipFuncGetAttributes(&fa, ks[i].fn));
-    if (names) names[i] = ks[i].name;
-    if (vgprs) vgprs[i] = fa.numRegs;
-    if (scratch_bytes) scratch_bytes[i] = (int32_t)fa.localSizeBytes;
-    if (lds_bytes) lds_bytes[i] = (int32_t)(fa.sharedSizeBytes + ks[i].dyn);
-  }
-  return GW_OK;
+  GW_DEV_GUARD(m);
+  const gw_kernel_entry ks[] = {
+      {"k_ds_batch", (const void*)k_ds_batch, 0},
+      {"k_ds_hidden", (const void*)k_ds_hidden, 0},
+      {"k_ds_forward", (const void*)k_ds_forward, fwd_lds(m)},
+      {"k_ds_rowstats", (const void*)k_ds_rowstats, 0},
+      {"k_ds_backward", (const void*)k_ds_backward, bwd_lds(m)},
+      {"k_ds_reduce_dh", (const void*)k_ds_reduce_dh, 0},
+      {"k_ds_dw1", (const void*)k_ds_dw1, 0},
+      {"k_ds_adam_w1", (const void*)k_ds_adam_w1, 0},
+      {"k_ds_zero_rows", (const void*)k_ds_zero_rows, 0}};
+  return gw_trainer_kernel_attrs(m, ks, cap, names, vgprs, scratch_bytes, lds_bytes, count);
 }
+
+float* gw_ds_dev_vectors(gw_deepsim* m) { return m->dev->par[0].get(); }

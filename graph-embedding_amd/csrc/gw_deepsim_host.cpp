@@ -16,17 +16,15 @@
 
 #include "gw_deepsim_internal.h"
 #include "gw_deepsim_law.h"
+#include "gw_trainer_fail.h"
 
 static thread_local std::string g_ds_err;
 
 int gw_deepsim_fail(gw_deepsim* m, int code, const char* fmt, ...) {
-  char buf[1024];
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
+  gw_trainer_vfail(m ? &m->err : nullptr, &g_ds_err, code, fmt, ap);
   va_end(ap);
-  if (m) m->err = buf;
-  g_ds_err = buf;
   return code;
 }
 
@@ -43,6 +41,7 @@ int gw_ds_dev_train(gw_deepsim* m, int64_t, int64_t, double*, void*) { return no
 int gw_ds_dev_gradients(gw_deepsim* m, int64_t, float*, float*, float*, float*) { return no_dev(m); }
 int gw_ds_dev_batch(gw_deepsim* m, int64_t, int32_t*, int32_t*, float*, int32_t*, float*) { return no_dev(m); }
 int gw_ds_dev_export(gw_deepsim* m, float* const*, float* const*, float* const*) { return no_dev(m); }
+float* gw_ds_dev_vectors(gw_deepsim* m) { return no_dev(m), nullptr; }
 #endif
 
 extern "C" const char* gw_deepsim_last_error(const gw_deepsim* m) { return m ? m->err.c_str() : g_ds_err.c_str(); }
@@ -439,7 +438,7 @@ extern "C" int gw_deepsim_export(gw_deepsim* m, float* const par[4], float* cons
 
 extern "C" int gw_deepsim_vectors_dev(gw_deepsim* m, float** ptr, int64_t* pitch) {
   if (!m || !ptr || !pitch) return gw_deepsim_fail(m, GW_ERR_INVALID, "NULL argument");
-  *ptr = m->device < 0 ? m->par[0].data() : m->d_par[0];
+  *ptr = m->device < 0 ? m->par[0].data() : gw_ds_dev_vectors(m);
   *pitch = m->p.dim;
   return GW_OK;
 }

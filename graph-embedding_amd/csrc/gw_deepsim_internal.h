@@ -29,39 +29,12 @@ struct gw_deepsim {
   std::vector<int32_t> elig_len;
   // host state (device = -1): par/am/av = {w1, b1, w2, b2}
   std::vector<float> par[4], am[4], av[4];
-  // device state
-  float* d_par[4] = {nullptr, nullptr, nullptr, nullptr};
-  float* d_am[4] = {nullptr, nullptr, nullptr, nullptr};
-  float* d_av[4] = {nullptr, nullptr, nullptr, nullptr};
-  float* d_gw1 = nullptr;     // [V][dim] gradient rows of w1, all 0 between steps
-  bool gw1_dirty = false;     // a call ended before its rows were zeroed again: the next call clears d_gw1
-  float* d_gsmall = nullptr;  // gb1 [dim]
-  float* d_gw2 = nullptr;     // diagnostic [dim][V] + gb2 [V], allocated by gw_deepsim_gradients
-  float* d_logits = nullptr;  // [B][V]
-  float* d_hidden = nullptr;  // [B][dim] hidden, then [B][dim] pre-activation
-  float* d_tmax = nullptr;    // [ntiles][B]
-  float* d_tsum = nullptr;    // [ntiles][B]
-  float* d_rowM = nullptr;    // [B] M, then [B] S
-  float* d_part = nullptr;    // [ntiles][B][dim]
-  float* d_dh = nullptr;      // [B][dim]
-  int32_t* d_centre = nullptr;
-  int32_t* d_tgt_id = nullptr;
-  float* d_tgt_val = nullptr;
-  int32_t* d_tgt_n = nullptr;
-  float* d_ysum = nullptr;
-  int32_t* d_tab_id = nullptr;
-  int32_t* d_tab_cnt = nullptr;
-  float* d_tab_val = nullptr;
-  float* d_tem = nullptr;
-  int64_t* d_labels = nullptr;
-  int64_t* d_elig = nullptr;
-  int32_t* d_elig_len = nullptr;
-  double* d_loss = nullptr;  // per-step losses of one train call
-  int64_t loss_cap = 0;
+  struct gw_deepsim_dev* dev = nullptr;  // device state (device >= 0), defined and owned by gw_deepsim.hip
   std::string err;
 };
 
 int gw_deepsim_fail(gw_deepsim* m, int code, const char* fmt, ...);
+inline auto gw_fail_of(const gw_deepsim*) { return &gw_deepsim_fail; }  // for the shared device plumbing
 inline size_t gw_ds_numel(const gw_deepsim* m, int t) {
   return t == 0 || t == 2 ? (size_t)m->V * (size_t)m->p.dim : (t == 1 ? (size_t)m->p.dim : (size_t)m->V);
 }
@@ -80,3 +53,4 @@ int gw_ds_dev_gradients(gw_deepsim* m, int64_t step, float* gw1, float* gb1, flo
 int gw_ds_dev_batch(gw_deepsim* m, int64_t step, int32_t* centre, int32_t* tgt_id, float* tgt_val, int32_t* tgt_n,
                     float* ysum);
 int gw_ds_dev_export(gw_deepsim* m, float* const par[4], float* const am[4], float* const av[4]);
+float* gw_ds_dev_vectors(gw_deepsim* m);  // w1 in device memory, [V][dim]

@@ -83,6 +83,43 @@ class gw_dev_scratch {
   std::vector<void*> bufs_;
 };
 
+// A device buffer that a handle (or a call) owns: freed when its owner goes
+// away, so a new buffer costs one member and one alloc() and has no entry in
+// any free list.  The capacity is in elements.
+template <typename T>
+class gw_dev_buf {
+ public:
+  gw_dev_buf() = default;
+  gw_dev_buf(const gw_dev_buf&) = delete;
+  gw_dev_buf& operator=(const gw_dev_buf&) = delete;
+  ~gw_dev_buf() { reset(); }
+
+  // Releases what it holds, then asks for `count` elements (count < 1: one
+  // element), in that order, so regrowing never holds both blocks.
+  hipError_t alloc(int64_t count) {
+    reset();
+    if (count < 1) count = 1;
+    const hipError_t e = hipMalloc((void**)&p_, sizeof(T) * (size_t)count);
+    cap_ = e == hipSuccess ? count : 0;
+    if (e != hipSuccess) p_ = nullptr;
+    return e;
+  }
+
+  hipError_t grow(int64_t need) { return need <= cap_ ? hipSuccess : alloc(need); }
+
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+    cap_ = 0;
+  }
+
+  T* get() const { return p_; }
+
+ private:
+  T* p_ = nullptr;
+  int64_t cap_ = 0;
+};
+
 // Runtime step -> compile-time constant: f(std::integral_constant<int, S>{})
 // for step S in 1..7 and S = 8 otherwise (callers validate step first).
 template <typename F>

@@ -19,8 +19,21 @@
 
 #include <algorithm>
 
-#include "gw_device_common.h"
 #include "gw_ovr_internal.h"
+#include "gw_trainer_device.h"
+
+// Device state of a gw_ovr handle (device >= 0); the buffers are freed with it.
+struct gw_ovr_dev {
+  gw_dev_buf<int64_t> row_off;
+  gw_dev_buf<int32_t> ids;
+  gw_dev_buf<int64_t> rows;  // gathered row list of the running call
+  gw_dev_buf<uint8_t> y;     // [T][L]
+  gw_dev_buf<double> z;      // [T][L] z, then [T][L] D; decision values when scoring
+  gw_dev_buf<double> part;   // [blocks][L][D]
+  gw_dev_buf<double> vec;    // 7 x [L][D]: q, w, wt, g, sv, r, p
+  gw_dev_buf<gw_ovr_label> lab;
+  gw_dev_buf<int64_t> counts;  // [L][3]
+};
 
 namespace {
 
@@ -209,124 +222,84 @@ __global__ void k_ovr_count(int L, const int64_t* __restrict__ rows, int64_t cou
   if (!pred && truth) atomicAdd(&counts[l * 3 + 2], 1ull);
 }
 
-#define OVR_TRY(expr)                                                                                    \
-  do {                                                                                                   \
-    hipError_t _e = (expr);                                                                              \
-    if (_e != hipSuccess) return gw_ovr_fail(m, GW_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
-
-#define OVR_GUARD(m)                   \
-  gw_device_guard gw_dg_((m)->device); \
-  if (!gw_dg_.ok) return gw_ovr_fail((m), GW_ERR_DEVICE, "cannot select HIP device %d", (m)->device)
-
-template <typename T>
-hipError_t dmalloc(T** p, size_t count) {
-  return hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-}
-
-template <typename T>
-int grow(gw_ovr* m, T** p, int64_t* cap, int64_t need, size_t per) {
-  if (need <= *cap) return GW_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (dmalloc(p, (size_t)need * per) != hipSuccess) return gw_ovr_fail(m, GW_ERR_NOMEM, "device allocation failed");
-  *cap = need;
-  return GW_OK;
-}
-
 size_t step_lds(const gw_ovr* m) { return (size_t)7 * m->D * sizeof(double); }
 
 // the gathered row list and the [rows][L] buffers of a call over `count` rows
 int stage_rows(gw_ovr* m, const int64_t* rows, int64_t count, hipStream_t st) {
-  int rc = grow(m, &m->d_rows, &m->rows_cap, count, 1);
-  if (rc != GW_OK) return rc;
-  if (count > m->zy_cap) {
-    if (m->d_y) (void)hipFree(m->d_y);
-    if (m->d_z) (void)hipFree(m->d_z);
-    m->d_y = nullptr;
-    m->d_z = nullptr;
-    m->zy_cap = 0;
-    if (dmalloc(&m->d_y, (size_t)count * m->L) != hipSuccess || dmalloc(&m->d_z, (size_t)2 * count * m->L) != hipSuccess)
-      return gw_ovr_fail(m, GW_ERR_NOMEM, "device allocation failed");
-    m->zy_cap = count;
-  }
-  OVR_TRY(hipMemcpyAsync(m->d_rows, rows, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  gw_ovr_dev& dv = *m->dev;
+  const int64_t cells = count * m->L;
+  if (dv.rows.grow(count) != hipSuccess || dv.y.grow(cells) != hipSuccess || dv.z.grow(2 * cells) != hipSuccess)
+    return gw_ovr_fail(m, GW_ERR_NOMEM, "device allocation failed");
+  GW_DEV_TRY(m, hipMemcpyAsync(dv.rows.get(), rows, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, st));
   return GW_OK;
 }
 
 OvrArgs make_args(const gw_ovr* m, int64_t T) {
+  const gw_ovr_dev& dv = *m->dev;
   OvrArgs A = {};
   A.x = m->x;
   A.pitch = m->pitch;
   A.vec16 = ((uintptr_t)m->x % 16 == 0 && m->pitch % 4 == 0) ? 1 : 0;
-  A.rows = m->d_rows;
+  A.rows = dv.rows.get();
   A.T = T;
   A.L = m->L;
   A.D = m->D;
-  A.y = m->d_y;
-  A.z = m->d_z;
-  A.Dd = m->d_z + (size_t)T * m->L;
-  A.part = m->d_part;
-  A.vec = m->d_vec;
-  A.lab = m->d_lab;
+  A.y = dv.y.get();
+  A.z = dv.z.get();
+  A.Dd = dv.z.get() + (size_t)T * m->L;
+  A.part = dv.part.get();
+  A.vec = dv.vec.get();
+  A.lab = dv.lab.get();
   return A;
 }
 
 }  // namespace
 
 int gw_ovr_dev_alloc(gw_ovr* m) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return gw_ovr_fail(m, GW_ERR_DEVICE, "no HIP device visible (device = -1 evaluates the law on the host)");
-  if (m->device >= count) return gw_ovr_fail(m, GW_ERR_INVALID, "device ordinal out of range");
-  OVR_GUARD(m);
-  hipError_t e = dmalloc(&m->d_vec, (size_t)7 * m->L * m->D);
-  if (e == hipSuccess) e = dmalloc(&m->d_lab, (size_t)m->L);
-  if (e == hipSuccess) e = dmalloc(&m->d_counts, (size_t)m->L * 3);
-  if (e == hipSuccess) e = dmalloc(&m->d_row_off, (size_t)m->n + 1);
+  const int rc = gw_trainer_open_device(m);
+  if (rc != GW_OK) return rc;
+  GW_DEV_GUARD(m);
+  gw_ovr_dev& dv = *m->dev;
+  hipError_t e = dv.vec.alloc((int64_t)7 * m->L * m->D);
+  if (e == hipSuccess) e = dv.lab.alloc(m->L);
+  if (e == hipSuccess) e = dv.counts.alloc((int64_t)m->L * 3);
+  if (e == hipSuccess) e = dv.row_off.alloc(m->n + 1);
   if (e != hipSuccess) return gw_ovr_fail(m, GW_ERR_NOMEM, "device allocation failed: %s", hipGetErrorString(e));
   return GW_OK;
 }
 
 void gw_ovr_dev_free(gw_ovr* m) {
   gw_device_guard dg(m->device);
-  void* ps[] = {m->d_row_off, m->d_ids, m->d_rows, m->d_y, m->d_z, m->d_part, m->d_vec, m->d_lab, m->d_counts};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  m->d_row_off = m->d_rows = m->d_counts = nullptr;
-  m->d_ids = nullptr;
-  m->d_y = nullptr;
-  m->d_z = m->d_part = m->d_vec = nullptr;
-  m->d_lab = nullptr;
+  delete m->dev;
+  m->dev = nullptr;
 }
 
 int gw_ovr_dev_upload_labels(gw_ovr* m) {
-  OVR_GUARD(m);
-  if (m->d_ids) (void)hipFree(m->d_ids);
-  m->d_ids = nullptr;
-  if (dmalloc(&m->d_ids, m->ids.size()) != hipSuccess) return gw_ovr_fail(m, GW_ERR_NOMEM, "device allocation failed");
-  OVR_TRY(hipMemcpy(m->d_row_off, m->row_off.data(), m->row_off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  if (!m->ids.empty())
-    OVR_TRY(hipMemcpy(m->d_ids, m->ids.data(), m->ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  GW_DEV_GUARD(m);
+  gw_ovr_dev& dv = *m->dev;
+  const size_t nnz = m->ids.size(), off_bytes = m->row_off.size() * sizeof(int64_t);
+  if (dv.ids.alloc((int64_t)nnz) != hipSuccess) return gw_ovr_fail(m, GW_ERR_NOMEM, "device allocation failed");
+  GW_DEV_TRY(m, hipMemcpy(dv.row_off.get(), m->row_off.data(), off_bytes, hipMemcpyHostToDevice));
+  if (nnz) GW_DEV_TRY(m, hipMemcpy(dv.ids.get(), m->ids.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice));
   return GW_OK;
 }
 
 int gw_ovr_dev_fit(gw_ovr* m, const int64_t* rows, int64_t T, const uint8_t* y, int64_t* passes, void* stream) {
-  OVR_GUARD(m);
+  GW_DEV_GUARD(m);
+  gw_ovr_dev& dv = *m->dev;
   hipStream_t st = (hipStream_t)stream;
   const int L = m->L, D = m->D;
-  const size_t LD = (size_t)L * D;
+  const size_t LD = (size_t)L * D, lab_bytes = (size_t)L * sizeof(gw_ovr_label);
   const int64_t nb = (T + kRB - 1) / kRB;
   if (nb > 0x7FFFFFFF) return gw_ovr_fail(m, GW_ERR_UNSUPPORTED, "too many rows for one launch");
   int rc = stage_rows(m, rows, T, st);
   if (rc != GW_OK) return rc;
-  rc = grow(m, &m->d_part, &m->part_cap, nb, LD);
-  if (rc != GW_OK) return rc;
-  OVR_TRY(hipMemcpyAsync(m->d_y, y, (size_t)T * L, hipMemcpyHostToDevice, st));
-  OVR_TRY(hipMemcpyAsync(m->d_lab, m->lab.data(), (size_t)L * sizeof(gw_ovr_label), hipMemcpyHostToDevice, st));
-  OVR_TRY(hipMemsetAsync(m->d_vec, 0, 7 * LD * sizeof(double), st));
-  OVR_TRY(hipStreamSynchronize(st));  // the caller's host arrays are read: no early return leaves a copy in flight
+  if (dv.part.grow(nb * (int64_t)LD) != hipSuccess) return gw_ovr_fail(m, GW_ERR_NOMEM, "device allocation failed");
+  GW_DEV_TRY(m, hipMemcpyAsync(dv.y.get(), y, (size_t)T * L, hipMemcpyHostToDevice, st));
+  GW_DEV_TRY(m, hipMemcpyAsync(dv.lab.get(), m->lab.data(), lab_bytes, hipMemcpyHostToDevice, st));
+  GW_DEV_TRY(m, hipMemsetAsync(dv.vec.get(), 0, 7 * LD * sizeof(double), st));
+  // the caller's host arrays are read: no early return leaves a copy in flight
+  GW_DEV_TRY(m, hipStreamSynchronize(st));
   const OvrArgs A = make_args(m, T);
   const gw_ovr_consts K = {m->p.C, m->p.gtol, m->p.max_newton, m->p.max_cg};
   const dim3 grid((unsigned)nb, (unsigned)((L + kLC - 1) / kLC));
@@ -337,50 +310,53 @@ int gw_ovr_dev_fit(gw_ovr* m, const int64_t* rows, int64_t T, const uint8_t* y, 
     k_ovr_pass<<<grid, kThreads, 0, st>>>(A);
     k_ovr_reduce<<<(unsigned)((LD + 255) / 256), 256, 0, st>>>(A, nb);
     k_ovr_step<<<L, kThreads, step_lds(m), st>>>(A, K);
-    OVR_TRY(hipGetLastError());
-    OVR_TRY(hipMemcpyAsync(m->lab.data(), m->d_lab, (size_t)L * sizeof(gw_ovr_label), hipMemcpyDeviceToHost, st));
-    OVR_TRY(hipStreamSynchronize(st));
+    GW_DEV_TRY(m, hipGetLastError());
+    GW_DEV_TRY(m, hipMemcpyAsync(m->lab.data(), dv.lab.get(), lab_bytes, hipMemcpyDeviceToHost, st));
+    GW_DEV_TRY(m, hipStreamSynchronize(st));
     *passes += 1;
   }
   m->W.resize(LD);
-  OVR_TRY(hipMemcpyAsync(m->W.data(), m->d_vec + LD, LD * sizeof(double), hipMemcpyDeviceToHost, st));
-  OVR_TRY(hipStreamSynchronize(st));
+  GW_DEV_TRY(m, hipMemcpyAsync(m->W.data(), dv.vec.get() + LD, LD * sizeof(double), hipMemcpyDeviceToHost, st));
+  GW_DEV_TRY(m, hipStreamSynchronize(st));
   return GW_OK;
 }
 
-// decision values of `rows` into d_z; the weights ride in d_vec's w slot (they are what the fit left there)
+// decision values of `rows` into z; the weights ride in vec's w slot (they are what the fit left there)
 static int launch_decision(gw_ovr* m, const int64_t* rows, int64_t count, hipStream_t st) {
+  gw_ovr_dev& dv = *m->dev;
   const int rc = stage_rows(m, rows, count, st);
   if (rc != GW_OK) return rc;
   const int64_t cells = count * m->L;
   if ((cells + 255) / 256 > 0x7FFFFFFF) return gw_ovr_fail(m, GW_ERR_UNSUPPORTED, "too many rows for one launch");
   const OvrArgs A = make_args(m, count);
-  k_ovr_decision<<<(unsigned)((cells + 255) / 256), 256, 0, st>>>(A, m->d_rows, count, m->d_vec + (size_t)m->L * m->D,
-                                                                  m->d_z);
-  OVR_TRY(hipGetLastError());
+  const double* w = dv.vec.get() + (size_t)m->L * m->D;
+  k_ovr_decision<<<(unsigned)((cells + 255) / 256), 256, 0, st>>>(A, dv.rows.get(), count, w, dv.z.get());
+  GW_DEV_TRY(m, hipGetLastError());
   return GW_OK;
 }
 
 int gw_ovr_dev_decision(gw_ovr* m, const int64_t* rows, int64_t count, double* z) {
-  OVR_GUARD(m);
+  GW_DEV_GUARD(m);
+  gw_ovr_dev& dv = *m->dev;
   const int rc = launch_decision(m, rows, count, nullptr);
   if (rc != GW_OK) return rc;
-  OVR_TRY(hipMemcpy(z, m->d_z, (size_t)count * m->L * sizeof(double), hipMemcpyDeviceToHost));
+  GW_DEV_TRY(m, hipMemcpy(z, dv.z.get(), (size_t)count * m->L * sizeof(double), hipMemcpyDeviceToHost));
   return GW_OK;
 }
 
 int gw_ovr_dev_score(gw_ovr* m, const int64_t* rows, int64_t count, int64_t* counts, void* stream) {
-  OVR_GUARD(m);
+  GW_DEV_GUARD(m);
+  gw_ovr_dev& dv = *m->dev;
   hipStream_t st = (hipStream_t)stream;
   const int rc = launch_decision(m, rows, count, st);
   if (rc != GW_OK) return rc;
   const int64_t cells = count * m->L;
-  OVR_TRY(hipMemsetAsync(m->d_counts, 0, (size_t)m->L * 3 * sizeof(int64_t), st));
-  k_ovr_count<<<(unsigned)((cells + 255) / 256), 256, 0, st>>>(m->L, m->d_rows, count, m->d_z, m->d_row_off, m->d_ids,
-                                                               (unsigned long long*)m->d_counts);
-  OVR_TRY(hipGetLastError());
-  OVR_TRY(hipMemcpyAsync(counts, m->d_counts, (size_t)m->L * 3 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  OVR_TRY(hipStreamSynchronize(st));
+  GW_DEV_TRY(m, hipMemsetAsync(dv.counts.get(), 0, (size_t)m->L * 3 * sizeof(int64_t), st));
+  k_ovr_count<<<(unsigned)((cells + 255) / 256), 256, 0, st>>>(m->L, dv.rows.get(), count, dv.z.get(), dv.row_off.get(),
+                                                               dv.ids.get(), (unsigned long long*)dv.counts.get());
+  GW_DEV_TRY(m, hipGetLastError());
+  GW_DEV_TRY(m, hipMemcpyAsync(counts, dv.counts.get(), (size_t)m->L * 3 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  GW_DEV_TRY(m, hipStreamSynchronize(st));
   return GW_OK;
 }
 
@@ -388,26 +364,12 @@ extern "C" int gw_ovr_kernel_attrs(gw_ovr* m, int cap, const char** names, int32
                                    int32_t* lds_bytes, int32_t* count) {
   if (!m) return gw_ovr_fail(nullptr, GW_ERR_INVALID, "NULL handle");
   if (m->device < 0) return gw_ovr_fail(m, GW_ERR_STATE, "host evaluation launches no kernel");
-  OVR_GUARD(m);
-  struct K {
-    const char* name;
-    const void* fn;
-    size_t dyn;
-  };
-  const K ks[] = {{"k_ovr_pass", (const void*)k_ovr_pass, 0},
-                  {"k_ovr_reduce", (const void*)k_ovr_reduce, 0},
-                  {"k_ovr_step", (const void*)k_ovr_step, step_lds(m)},
-                  {"k_ovr_decision", (const void*)k_ovr_decision, 0},
-                  {"k_ovr_count", (const void*)k_ovr_count, 0}};
-  const int n = (int)(sizeof ks / sizeof ks[0]);
-  if (count) *count = n;
-  for (int i = 0; i < n && i < cap; ++i) {
-    hipFuncAttributes fa;
-    OVR_TRY(hipFuncGetAttributes(&fa, ks[i].fn));
-    if (names) names[i] = ks[i].name;
-    if (vgprs) vgprs[i] = fa.numRegs;
-    if (scratch_bytes) scratch_bytes[i] = (int32_t)fa.localSizeBytes;
-    if (lds_bytes) lds_bytes[i] = (int32_t)(fa.sharedSizeBytes + ks[i].dyn);
-  }
-  return GW_OK;
+  GW_DEV_GUARD(m);
+  const gw_kernel_entry ks[] = {
+      {"k_ovr_pass", (const void*)k_ovr_pass, 0},
+      {"k_ovr_reduce", (const void*)k_ovr_reduce, 0},
+      {"k_ovr_step", (const void*)k_ovr_step, step_lds(m)},
+      {"k_ovr_decision", (const void*)k_ovr_decision, 0},
+      {"k_ovr_count", (const void*)k_ovr_count, 0}};
+  return gw_trainer_kernel_attrs(m, ks, cap, names, vgprs, scratch_bytes, lds_bytes, count);
 }

@@ -13,17 +13,15 @@
 #include <new>
 
 #include "gw_ovr_internal.h"
+#include "gw_trainer_fail.h"
 
 static thread_local std::string g_ovr_err;
 
 int gw_ovr_fail(gw_ovr* m, int code, const char* fmt, ...) {
-  char buf[1024];
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
+  gw_trainer_vfail(m ? &m->err : nullptr, &g_ovr_err, code, fmt, ap);
   va_end(ap);
-  if (m) m->err = buf;
-  g_ovr_err = buf;
   return code;
 }
 

@@ -22,23 +22,12 @@ struct gw_ovr {
   // per-label solver state and results (host copies on both paths after a fit)
   std::vector<gw_ovr_label> lab;  // [L]
   std::vector<double> W;          // [L][D]
-  // device state
-  int64_t* d_row_off = nullptr;
-  int32_t* d_ids = nullptr;
-  int64_t* d_rows = nullptr;  // gathered row list of the running call
-  int64_t rows_cap = 0;
-  uint8_t* d_y = nullptr;     // [T][L]
-  double* d_z = nullptr;      // [T][L] z, then [T][L] D; decision values when scoring
-  int64_t zy_cap = 0;         // rows d_y / d_z hold
-  double* d_part = nullptr;   // [blocks][L][D]
-  int64_t part_cap = 0;       // blocks
-  double* d_vec = nullptr;    // 7 x [L][D]: q, w, wt, g, sv, r, p
-  gw_ovr_label* d_lab = nullptr;
-  int64_t* d_counts = nullptr;  // [L][3]
+  struct gw_ovr_dev* dev = nullptr;  // device state (device >= 0), defined and owned by gw_ovr.hip
   std::string err;
 };
 
 int gw_ovr_fail(gw_ovr* m, int code, const char* fmt, ...);
+inline auto gw_fail_of(const gw_ovr*) { return &gw_ovr_fail; }  // for the shared device plumbing
 
 // device entry points (gw_ovr.hip)
 int gw_ovr_dev_alloc(gw_ovr* m);

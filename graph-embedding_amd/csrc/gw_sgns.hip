@@ -20,9 +20,9 @@
 // the same row, in which case the updated registers carry over.
 #include <hip/hip_runtime.h>
 
-#include "gw_device_common.h"
 #include "gw_sgns_internal.h"
 #include "gw_sgns_law.h"
+#include "gw_trainer_device.h"
 
 namespace {
 
@@ -246,91 +246,86 @@ const void* train_kernel(int pitch) {
   }
 }
 
-#define SGNS_TRY(expr)                                                                        \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) return gw_sgns_fail(m, GW_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
-
-#define SGNS_GUARD(m)                \
-  gw_device_guard gw_dg_((m)->device); \
-  if (!gw_dg_.ok) return gw_sgns_fail((m), GW_ERR_DEVICE, "cannot select HIP device %d", (m)->device)
-
 }  // namespace
 
+// Device state of a gw_sgns handle (device >= 0); the buffers are freed with it.
+struct gw_sgns_dev {
+  gw_dev_buf<unsigned long long> counts;
+  gw_dev_buf<int32_t> J;
+  gw_dev_buf<uint32_t> thr, keep;
+  gw_dev_buf<float> expt, syn0, syn1;
+  gw_dev_buf<long long> stats;  // 5 stats + 1 error flag (8 allocated)
+  int cus = 0;
+};
+
 int gw_sgns_dev_alloc(gw_sgns* m) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return gw_sgns_fail(m, GW_ERR_DEVICE, "no HIP device visible (device = -1 evaluates the law on the host)");
-  if (m->device >= count) return gw_sgns_fail(m, GW_ERR_INVALID, "device ordinal out of range");
-  SGNS_GUARD(m);
+  const int rc = gw_trainer_open_device(m);
+  if (rc != GW_OK) return rc;
+  GW_DEV_GUARD(m);
+  gw_sgns_dev& dv = *m->dev;
   hipDeviceProp_t prop;
-  SGNS_TRY(hipGetDeviceProperties(&prop, m->device));
-  m->cus = prop.multiProcessorCount;
-  const size_t n = (size_t)m->n, rows = n * (size_t)m->pitch * sizeof(float);
-  hipError_t e = hipMalloc((void**)&m->d_counts, n * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&m->d_J, n * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc((void**)&m->d_thr, n * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc((void**)&m->d_keep, n * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc((void**)&m->d_expt, GW_SGNS_EXP_SIZE * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&m->d_syn0, rows);
-  if (e == hipSuccess) e = hipMalloc((void**)&m->d_syn1, rows);
-  if (e == hipSuccess) e = hipMalloc((void**)&m->d_stats, 8 * sizeof(long long));
+  GW_DEV_TRY(m, hipGetDeviceProperties(&prop, m->device));
+  dv.cus = prop.multiProcessorCount;
+  const int64_t n = m->n, rows = n * m->pitch;
+  hipError_t e = dv.counts.alloc(n);
+  if (e == hipSuccess) e = dv.J.alloc(n);
+  if (e == hipSuccess) e = dv.thr.alloc(n);
+  if (e == hipSuccess) e = dv.keep.alloc(n);
+  if (e == hipSuccess) e = dv.expt.alloc(GW_SGNS_EXP_SIZE);
+  if (e == hipSuccess) e = dv.syn0.alloc(rows);
+  if (e == hipSuccess) e = dv.syn1.alloc(rows);
+  if (e == hipSuccess) e = dv.stats.alloc(8);
   if (e != hipSuccess) return gw_sgns_fail(m, GW_ERR_NOMEM, "device allocation failed: %s", hipGetErrorString(e));
   return GW_OK;
 }
 
 void gw_sgns_dev_free(gw_sgns* m) {
   gw_device_guard dg(m->device);
-  void* ps[] = {m->d_counts, m->d_J, m->d_thr, m->d_keep, m->d_expt, m->d_syn0, m->d_syn1, m->d_stats};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  m->d_counts = nullptr;
-  m->d_J = nullptr;
-  m->d_thr = m->d_keep = nullptr;
-  m->d_expt = m->d_syn0 = m->d_syn1 = nullptr;
-  m->d_stats = nullptr;
+  delete m->dev;
+  m->dev = nullptr;
 }
 
 int gw_sgns_dev_count(gw_sgns* m, const int32_t* walks_dev, int64_t nwalks, int walk_len) {
-  SGNS_GUARD(m);
-  unsigned long long* flag = (unsigned long long*)m->d_stats;
-  SGNS_TRY(hipMemset(m->d_counts, 0, (size_t)m->n * sizeof(unsigned long long)));
-  SGNS_TRY(hipMemset(flag, 0, sizeof(unsigned long long)));
+  GW_DEV_GUARD(m);
+  gw_sgns_dev& dv = *m->dev;
+  unsigned long long* flag = (unsigned long long*)dv.stats.get();
+  GW_DEV_TRY(m, hipMemset(dv.counts.get(), 0, (size_t)m->n * sizeof(unsigned long long)));
+  GW_DEV_TRY(m, hipMemset(flag, 0, sizeof(unsigned long long)));
   if (nwalks > 0) {
     const int64_t blocks = (nwalks + 255) / 256;
     if (blocks > 0x7FFFFFFF) return gw_sgns_fail(m, GW_ERR_UNSUPPORTED, "too many walks for one launch");
-    k_sgns_count<<<(unsigned)blocks, 256>>>(walks_dev, nwalks, walk_len, m->n, m->d_counts, flag);
-    SGNS_TRY(hipGetLastError());
+    k_sgns_count<<<(unsigned)blocks, 256>>>(walks_dev, nwalks, walk_len, m->n, dv.counts.get(), flag);
+    GW_DEV_TRY(m, hipGetLastError());
   }
   unsigned long long bad = 0;
-  SGNS_TRY(hipMemcpy(&bad, flag, sizeof bad, hipMemcpyDeviceToHost));
+  GW_DEV_TRY(m, hipMemcpy(&bad, flag, sizeof bad, hipMemcpyDeviceToHost));
   if (bad) return gw_sgns_fail(m, GW_ERR_RANGE, "walk %lld holds an id outside [0, %lld)", (long long)bad - 1, (long long)m->n);
   std::vector<unsigned long long> c((size_t)m->n);
-  SGNS_TRY(hipMemcpy(c.data(), m->d_counts, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  GW_DEV_TRY(m, hipMemcpy(c.data(), dv.counts.get(), c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   m->counts.resize((size_t)m->n);
   for (size_t v = 0; v < c.size(); ++v) m->counts[v] = (int64_t)c[v];
   return GW_OK;
 }
 
 int gw_sgns_dev_upload_vocab(gw_sgns* m) {
-  SGNS_GUARD(m);
+  GW_DEV_GUARD(m);
+  gw_sgns_dev& dv = *m->dev;
   const size_t n = (size_t)m->n;
-  SGNS_TRY(hipMemcpy(m->d_J, m->J.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-  SGNS_TRY(hipMemcpy(m->d_thr, m->thr.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-  SGNS_TRY(hipMemcpy(m->d_keep, m->keep_thr.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-  SGNS_TRY(hipMemcpy(m->d_expt, m->expt.data(), GW_SGNS_EXP_SIZE * sizeof(float), hipMemcpyHostToDevice));
-  SGNS_TRY(hipMemset(m->d_syn1, 0, n * (size_t)m->pitch * sizeof(float)));
+  GW_DEV_TRY(m, hipMemcpy(dv.J.get(), m->J.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+  GW_DEV_TRY(m, hipMemcpy(dv.thr.get(), m->thr.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  GW_DEV_TRY(m, hipMemcpy(dv.keep.get(), m->keep_thr.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  GW_DEV_TRY(m, hipMemcpy(dv.expt.get(), m->expt.data(), GW_SGNS_EXP_SIZE * sizeof(float), hipMemcpyHostToDevice));
+  GW_DEV_TRY(m, hipMemset(dv.syn1.get(), 0, n * (size_t)m->pitch * sizeof(float)));
   const int64_t total = m->n * m->pitch, blocks = (total + 255) / 256;
   if (blocks > 0x7FFFFFFF) return gw_sgns_fail(m, GW_ERR_UNSUPPORTED, "n * dim too large for one launch");
-  k_sgns_init<<<(unsigned)blocks, 256>>>(m->d_syn0, m->n, m->pitch, m->p.dim, m->p.seed);
-  SGNS_TRY(hipGetLastError());
-  SGNS_TRY(hipDeviceSynchronize());
+  k_sgns_init<<<(unsigned)blocks, 256>>>(dv.syn0.get(), m->n, m->pitch, m->p.dim, m->p.seed);
+  GW_DEV_TRY(m, hipGetLastError());
+  GW_DEV_TRY(m, hipDeviceSynchronize());
   return GW_OK;
 }
 
 int gw_sgns_auto_concurrency(const gw_sgns* m, int64_t nwalks) {
-  int64_t c = std::min<int64_t>(nwalks, 16 * (int64_t)std::max(m->cus, 1));
+  int64_t c = std::min<int64_t>(nwalks, 16 * (int64_t)std::max(m->dev->cus, 1));
   c = std::min<int64_t>(c, std::max<int64_t>(1, m->n / 32));
   return (int)std::max<int64_t>(c, 1);
 }
@@ -339,7 +334,8 @@ int gw_sgns_dev_train(gw_sgns* m, const int32_t* walks_dev, int64_t nwalks, int 
                       int epoch_count, int concurrency, int64_t* stats, void* stream) {
   if (walk_len > kMaxWalkLen)
     return gw_sgns_fail(m, GW_ERR_UNSUPPORTED, "walk_len %d: the kernel keeps a walk in LDS (<= %d)", walk_len, kMaxWalkLen);
-  SGNS_GUARD(m);
+  GW_DEV_GUARD(m);
+  gw_sgns_dev& dv = *m->dev;
   hipStream_t st = (hipStream_t)stream;
   int conc = concurrency > 0 ? concurrency : gw_sgns_auto_concurrency(m, nwalks);
   conc = (int)std::min<int64_t>(conc, nwalks);
@@ -356,39 +352,36 @@ int gw_sgns_dev_train(gw_sgns* m, const int32_t* walks_dev, int64_t nwalks, int 
   A.alpha0 = m->p.alpha;
   A.min_alpha = m->p.min_alpha;
   A.seed = m->p.seed;
-  A.J = m->d_J;
-  A.thr = m->d_thr;
-  A.keep = m->d_keep;
-  A.expt = m->d_expt;
-  A.syn0 = m->d_syn0;
-  A.syn1 = m->d_syn1;
-  A.stats = (unsigned long long*)m->d_stats;
-  SGNS_TRY(hipMemsetAsync(m->d_stats, 0, 8 * sizeof(long long), st));
+  A.J = dv.J.get();
+  A.thr = dv.thr.get();
+  A.keep = dv.keep.get();
+  A.expt = dv.expt.get();
+  A.syn0 = dv.syn0.get();
+  A.syn1 = dv.syn1.get();
+  A.stats = (unsigned long long*)dv.stats.get();
+  GW_DEV_TRY(m, hipMemsetAsync(dv.stats.get(), 0, 8 * sizeof(long long), st));
   const void* fn = train_kernel(m->pitch);
   const unsigned grid = (unsigned)((conc + kWaves - 1) / kWaves);
   const size_t lds = (size_t)kWaves * 2 * (size_t)walk_len * sizeof(int32_t);
   for (int e = epoch_begin; e < epoch_begin + epoch_count; ++e) {
     A.epoch = e;
     void* args[] = {&A};
-    SGNS_TRY(hipLaunchKernel(fn, dim3(grid), dim3(kWaves * GW_SGNS_LANES), args, lds, st));
+    GW_DEV_TRY(m, hipLaunchKernel(fn, dim3(grid), dim3(kWaves * GW_SGNS_LANES), args, lds, st));
   }
   long long h[8];
-  SGNS_TRY(hipMemcpyAsync(h, m->d_stats, sizeof h, hipMemcpyDeviceToHost, st));
-  SGNS_TRY(hipStreamSynchronize(st));
+  GW_DEV_TRY(m, hipMemcpyAsync(h, dv.stats.get(), sizeof h, hipMemcpyDeviceToHost, st));
+  GW_DEV_TRY(m, hipStreamSynchronize(st));
   if (h[5]) return gw_sgns_fail(m, GW_ERR_RANGE, "the walks hold an id outside [0, %lld)", (long long)m->n);
   for (int i = 0; i < 5; ++i) stats[i] = h[i];
   return GW_OK;
 }
 
 int gw_sgns_dev_export(gw_sgns* m, float* syn0, float* syn1neg) {
-  SGNS_GUARD(m);
-  const size_t dim = (size_t)m->p.dim;
-  if (syn0)
-    SGNS_TRY(hipMemcpy2D(syn0, dim * sizeof(float), m->d_syn0, (size_t)m->pitch * sizeof(float), dim * sizeof(float),
-                         (size_t)m->n, hipMemcpyDeviceToHost));
-  if (syn1neg)
-    SGNS_TRY(hipMemcpy2D(syn1neg, dim * sizeof(float), m->d_syn1, (size_t)m->pitch * sizeof(float), dim * sizeof(float),
-                         (size_t)m->n, hipMemcpyDeviceToHost));
+  GW_DEV_GUARD(m);
+  gw_sgns_dev& dv = *m->dev;
+  const size_t row = (size_t)m->p.dim * sizeof(float), pitch = (size_t)m->pitch * sizeof(float), n = (size_t)m->n;
+  if (syn0) GW_DEV_TRY(m, hipMemcpy2D(syn0, row, dv.syn0.get(), pitch, row, n, hipMemcpyDeviceToHost));
+  if (syn1neg) GW_DEV_TRY(m, hipMemcpy2D(syn1neg, row, dv.syn1.get(), pitch, row, n, hipMemcpyDeviceToHost));
   return GW_OK;
 }
 
@@ -397,11 +390,13 @@ extern "C" int gw_sgns_kernel_attrs(gw_sgns* m, int walk_len, int32_t* vgprs, in
   if (!m) return gw_sgns_fail(nullptr, GW_ERR_INVALID, "NULL handle");
   if (m->device < 0) return gw_sgns_fail(m, GW_ERR_STATE, "host evaluation launches no kernel");
   if (walk_len < 1 || walk_len > kMaxWalkLen) return gw_sgns_fail(m, GW_ERR_INVALID, "walk_len %d", walk_len);
-  SGNS_GUARD(m);
+  GW_DEV_GUARD(m);
   hipFuncAttributes fa;
-  SGNS_TRY(hipFuncGetAttributes(&fa, train_kernel(m->pitch)));
+  GW_DEV_TRY(m, hipFuncGetAttributes(&fa, train_kernel(m->pitch)));
   if (vgprs) *vgprs = fa.numRegs;
   if (scratch_bytes) *scratch_bytes = (int32_t)fa.localSizeBytes;
   if (lds_bytes) *lds_bytes = (int32_t)(fa.sharedSizeBytes + (size_t)kWaves * 2 * (size_t)walk_len * sizeof(int32_t));
   return GW_OK;
 }
+
+float* gw_sgns_dev_vectors(gw_sgns* m) { return m->dev->syn0.get(); }

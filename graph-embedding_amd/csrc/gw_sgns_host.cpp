@@ -12,15 +12,16 @@
 #include "gw_internal.h"
 #include "gw_sgns_internal.h"
 #include "gw_sgns_law.h"
+#include "gw_trainer_fail.h"
 
+// the handle-less error of this family is the library-wide one (gw_last_error(NULL))
 int gw_sgns_fail(gw_sgns* m, int code, const char* fmt, ...) {
-  char buf[1024];
+  std::string tls;
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
+  gw_trainer_vfail(m ? &m->err : nullptr, &tls, code, fmt, ap);
   va_end(ap);
-  if (m) m->err = buf;
-  gw_set_tls_error(buf);
+  gw_set_tls_error(tls);
   return code;
 }
 
@@ -312,7 +313,7 @@ extern "C" int gw_sgns_sampler_export(const gw_sgns* m, int32_t* J, uint32_t* th
 extern "C" int gw_sgns_vectors_dev(gw_sgns* m, float** ptr, int64_t* pitch) {
   if (!m || !ptr || !pitch) return gw_sgns_fail(m, GW_ERR_INVALID, "NULL argument");
   if (!m->vocab) return gw_sgns_fail(m, GW_ERR_STATE, "call gw_sgns_build_vocab first");
-  *ptr = m->device < 0 ? m->syn0.data() : m->d_syn0;
+  *ptr = m->device < 0 ? m->syn0.data() : gw_sgns_dev_vectors(m);
   *pitch = m->pitch;
   return GW_OK;
 }

@@ -20,20 +20,12 @@ struct gw_sgns {
   std::vector<uint32_t> thr, keep_thr;
   std::vector<float> expt;
   std::vector<float> syn0, syn1;  // device = -1 only, [n][pitch]
-  // device side (device >= 0)
-  unsigned long long* d_counts = nullptr;
-  int32_t* d_J = nullptr;
-  uint32_t* d_thr = nullptr;
-  uint32_t* d_keep = nullptr;
-  float* d_expt = nullptr;
-  float* d_syn0 = nullptr;
-  float* d_syn1 = nullptr;
-  long long* d_stats = nullptr;  // 5 stats + 1 error flag
-  int cus = 0;
+  struct gw_sgns_dev* dev = nullptr;  // device state (device >= 0), defined and owned by gw_sgns.hip
   std::string err;
 };
 
 int gw_sgns_fail(gw_sgns* m, int code, const char* fmt, ...);
+inline auto gw_fail_of(const gw_sgns*) { return &gw_sgns_fail; }  // for the shared device plumbing
 
 // device entry points (gw_sgns.hip)
 int gw_sgns_dev_alloc(gw_sgns* m);
@@ -43,4 +35,5 @@ int gw_sgns_dev_upload_vocab(gw_sgns* m);                                       
 int gw_sgns_dev_train(gw_sgns* m, const int32_t* walks_dev, int64_t nwalks, int walk_len, int epoch_begin,
                       int epoch_count, int concurrency, int64_t* stats, void* stream);
 int gw_sgns_dev_export(gw_sgns* m, float* syn0, float* syn1neg);
+float* gw_sgns_dev_vectors(gw_sgns* m);  // syn0 in device memory, [n][pitch]
 int gw_sgns_auto_concurrency(const gw_sgns* m, int64_t nwalks);
