@@ -13,6 +13,10 @@ Host-side mirror of the reference interfaces over the libgraphwalk C ABI
 * `gwamd.classify`  — classify.scoring (node2vec/src/classify.py): one-vs-rest logistic
                       regression on the device-resident embedding, top-k prediction,
                       micro- / macro-F1; `python -m gwamd.classify --emb X --groups G`
+* `gwamd.neighbors` — KeyedVectors.most_similar (DeepSim/src/main.py:287): all-pairs top-k
+                      cosine / dot neighbours of the device-resident embedding, in gw_topsim's
+                      row layout; label_agreement (preprocess_simrank);
+                      `python -m gwamd.neighbors --emb X --output X.nn`
 * `gwamd.topsim`    — DeepSim/TopSimAll structures.Graph, TopSim_singleSample,
                       TopSim_Enumerate, SingleRandomWalk, SimRank (naive),
                       Print.printByOrder/printByOrderAll,
@@ -24,7 +28,8 @@ Host-side mirror of the reference interfaces over the libgraphwalk C ABI
 from . import _lib
 from ._lib import device_count, lib
 from . import classify
+from . import neighbors
 from .graph import GWGraph
 
-__all__ = ["GWGraph", "classify", "device_count", "lib", "_lib"]
+__all__ = ["GWGraph", "classify", "neighbors", "device_count", "lib", "_lib"]
 __version__ = "0.1.0"

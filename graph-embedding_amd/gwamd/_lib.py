@@ -144,6 +144,19 @@ class OvrStats(ctypes.Structure):
                 ("not_converged", ctypes.c_int32), ("newton_max", ctypes.c_int32)]
 
 
+KNN_COSINE = 0
+KNN_DOT = 1
+
+
+class KnnParams(ctypes.Structure):
+    """gw_knn_params_t (include/graphwalk.h); struct_size is filled in by default."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("dim", ctypes.c_int32), ("topk", ctypes.c_int32),
+                ("metric", ctypes.c_int32)]
+
+    def __init__(self, dim=128, topk=20, metric=KNN_COSINE):
+        super().__init__(ctypes.sizeof(KnnParams), dim, topk, metric)
+
+
 P = ctypes.c_void_p
 I32 = ctypes.c_int32
 I64 = ctypes.c_int64
@@ -246,6 +259,16 @@ SIGNATURES = {
     "gw_ovr_decision": (ctypes.c_int, [P, P, I64, P]),
     "gw_ovr_export": (ctypes.c_int, [P, P, P, P, P]),
     "gw_ovr_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
+    "gw_knn_create": (ctypes.c_int, [ctypes.c_int, I64, ctypes.POINTER(KnnParams), PP]),
+    "gw_knn_free": (ctypes.c_int, [P]),
+    "gw_knn_last_error": (CP, [P]),
+    "gw_knn_set_vectors": (ctypes.c_int, [P, P, I64]),
+    "gw_knn_set_rows": (ctypes.c_int, [P, I64]),
+    "gw_knn_query": (ctypes.c_int, [P, P, I64, P, P, P]),
+    "gw_knn_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
+    "gw_knn_tiles": (ctypes.c_int, [P, PI32, PI32, PI32, PI32]),
+    "gw_knn_fma_rate": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, PD]),
+    "gw_topk_label_agreement": (ctypes.c_int, [P, I64, ctypes.c_int, P, P, P, I64, P]),
     "gw_comm_unique_id": (ctypes.c_int, [P]),
     "gw_comm_init": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, PP]),
     "gw_comm_allgather": (ctypes.c_int, [P, P, P, I64, ctypes.c_int, P]),
@@ -273,13 +296,15 @@ def lib():
     return _lib
 
 
-def check(rc, handle=None, sgns=None, deepsim=None, ovr=None):
+def check(rc, handle=None, sgns=None, deepsim=None, ovr=None, knn=None):
     """Raise for a failing status; `handle` a gw_graph, `sgns` a gw_sgns, `deepsim` a gw_deepsim or True for a
-    handle-less gw_deepsim call, `ovr` likewise for gw_ovr (for the message)."""
+    handle-less gw_deepsim call, `ovr` and `knn` likewise for gw_ovr and gw_knn (for the message)."""
     if rc == GW_OK:
         return
     L = lib()
-    if ovr is not None:
+    if knn is not None:
+        msg = L.gw_knn_last_error(None if knn is True else knn)
+    elif ovr is not None:
         msg = L.gw_ovr_last_error(None if ovr is True else ovr)
     elif deepsim is not None:
         msg = L.gw_deepsim_last_error(None if deepsim is True else deepsim)

@@ -47,6 +47,9 @@ def parse_args(argv=None, p=1.0, q=1.0):
                          "on rank 0 only when launched with several ranks.  Omitted: walks only")
     ap.add_argument("--groups", default=None, help="lines `node,label`: with --output, score the embeddings where they lie in "
                          "HBM by one-vs-rest logistic regression F1 (gwamd.classify.scoring)")
+    ap.add_argument("--neighbors", default=None, help="with --output: the 20 nearest neighbours (cosine) of every embedded "
+                         "vertex, computed where the embedding lies in HBM (gwamd.neighbors): rows `v,id,...` and "
+                         "NEIGHBORS.sim.txt with `v,id:score,...`; with --groups also their label agreement")
     ap.add_argument("--walks", default="walks.txt", help="walks output (save_list format, or .npy)")
     ap.add_argument("--dimensions", type=int, default=128)
     ap.add_argument("--walk-length", type=int, default=80)
@@ -203,6 +206,14 @@ def _embed(args, walks, labels, device):
     if args.groups:
         from . import classify
         classify.scoring(emb, classify.read_groups(args.groups), seed=args.seed, device=device)
+    if args.neighbors:
+        from . import neighbors
+        x, labels = emb, emb.labels
+        if not (emb.counts > 0).all():  # as the saved file: only the vertices that occur in a walk
+            keep = np.nonzero(emb.counts > 0)[0]
+            x, _ = neighbors._vectors_of(emb, device)
+            x, labels = (x[keep] if isinstance(x, np.ndarray) else x[keep.tolist()]), emb.labels[keep]
+        neighbors.neighbors_of(x, args.neighbors, labels, device=device, groups=args.groups)
 
 
 def main(argv=None):

@@ -233,6 +233,10 @@ def parse_args(argv=None):
     ap.add_argument("--emb_output", nargs="?", default="../emb/blog.emb")
     ap.add_argument("--groups", default=None, help="lines `node,label` (node = embedding row): score the embedding "
                                                    "where it lies in HBM (main.py:287-289, classify.scoring)")
+    ap.add_argument("--neighbors", default=None, help="the 20 nearest neighbours (cosine) of every embedding row, computed "
+                                                      "where the embedding lies in HBM (gwamd.neighbors): rows "
+                                                      "`v,id,...` and NEIGHBORS.sim.txt with `v,id:score,...`; with "
+                                                      "--groups also their label agreement")
     ap.add_argument("--TOPK", default=1000, type=int)
     ap.add_argument("--vertex-num", type=int, default=10313)
     ap.add_argument("--dimensions", type=int, default=128)
@@ -295,6 +299,9 @@ def cli(argv=None):
         from . import classify
         _, _, row_off, ids = classify.groups_csr(classify.read_groups(args.groups), range(m.V))
         classify.scoring(m, (row_off, ids), seed=args.seed, device=args.device)
+    if args.neighbors:
+        from . import neighbors
+        neighbors.neighbors_of(m, args.neighbors, range(m.V), device=args.device, groups=args.groups)
     return 0
 
 

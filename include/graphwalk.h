@@ -777,6 +777,79 @@ int gw_ovr_export(gw_ovr* m, double* W, int32_t* state, int32_t* newton_iters, d
 int gw_ovr_kernel_attrs(gw_ovr* m, int cap, const char** names, int32_t* vgprs, int32_t* scratch_bytes,
                         int32_t* lds_bytes, int32_t* count);
 
+/* ---- nearest neighbours of an embedding -------------------------------------- */
+/* Replaces KeyedVectors.most_similar (DeepSim/src/main.py:287 loads the result
+ * as KeyedVectors; cosine top-n) and IsoMap_LE/LE.py:53-60 knn: for every
+ * source row the topk other rows of largest similarity, in gw_topsim's row
+ * layout, so gw_write_sim_text_topk and topsim.precision read them as they are.
+ * csrc/gw_knn_law.h holds the one definition the kernels and the host
+ * evaluation (device = -1) share; they agree bit for bit (tested).
+ *   arithmetic  features are the caller's fp32 widened, everything else fp64;
+ *   dot(i,j)    fma over k = 0 .. dim-1 ascending from +0: no split-K, no
+ *               reassociation, dot(i,j) and dot(j,i) have the same bits;
+ *   nrm(i)      sqrt(dot(i,i)), correctly rounded;
+ *   GW_KNN_DOT     s(i,j) = dot(i,j);
+ *   GW_KNN_COSINE  s(i,j) = dot(i,j) / (nrm(i) * nrm(j)), one multiply and one
+ *               divide; a row with nrm == 0 has no neighbours and is nobody's;
+ *   row of v    the topk candidates j != v of largest s(v,j); a NaN score is
+ *               never listed; score descending, then id ascending (a total
+ *               order: nothing depends on tiles, grid or timing); a row with
+ *               fewer listed candidates is padded with (-1, 0.0).
+ * Device path: 1 <= dim <= 1024, 1 <= topk <= 128, n < 2^31 (else
+ * GW_ERR_UNSUPPORTED); the host path takes any size.                          */
+#define GW_KNN_COSINE 0
+#define GW_KNN_DOT 1
+typedef struct gw_knn gw_knn;
+typedef struct gw_knn_params_t {
+  int32_t struct_size; /* as gw_sgns_params_t.struct_size                      */
+  int32_t dim;         /* columns read of a row (128)                          */
+  int32_t topk;        /* entries per output row (20)                          */
+  int32_t metric;      /* GW_KNN_COSINE (default) or GW_KNN_DOT                */
+} gw_knn_params_t;
+/* device >= 0: a GPU; -1: the host evaluation.  n = rows of the matrix         */
+int gw_knn_create(int device, int64_t n, const gw_knn_params_t* params, gw_knn** out);
+int gw_knn_free(gw_knn* m);
+const char* gw_knn_last_error(const gw_knn* m);
+/* As gw_ovr_set_features: row v at x + v * pitch floats (pitch >= dim), device
+ * memory for device >= 0 and read where it lies (zero-copy from
+ * gw_sgns_vectors_dev / gw_deepsim_vectors_dev), host memory for device = -1.
+ * It must outlive the queries; only dim floats of a row are ever read.
+ * gw_knn_set_rows changes n for a handle that is used again on another matrix
+ * (call it before gw_knn_set_vectors).                                        */
+int gw_knn_set_vectors(gw_knn* m, const float* x, int64_t pitch);
+int gw_knn_set_rows(gw_knn* m, int64_t n);
+/* out_ids[r * topk + t] (int32) and out_scores[r * topk + t] (double) of the
+ * source sources[r], r < nsrc.  sources, out_ids and out_scores are device
+ * memory for device >= 0 and host memory for -1.  sources == NULL: all of
+ * 0 .. n-1 (nsrc is ignored).  Sources may repeat, in any order.  nsrc == 0
+ * returns GW_OK and does nothing.  A source outside [0, n) gives GW_ERR_RANGE
+ * and nothing is written.  GW_ERR_STATE before gw_knn_set_vectors.  Runs on
+ * `stream` and synchronises it.                                               */
+int gw_knn_query(gw_knn* m, const int32_t* sources, int64_t nsrc, int32_t* out_ids, double* out_scores,
+                 void* stream);
+/* As gw_ovr_kernel_attrs                                                      */
+int gw_knn_kernel_attrs(gw_knn* m, int cap, const char** names, int32_t* vgprs, int32_t* scratch_bytes,
+                        int32_t* lds_bytes, int32_t* count);
+/* Launch geometry of the main kernel (tests place their shapes on its edges):
+ * tq source rows per workgroup, tc candidate rows per tile, kc columns per LDS
+ * chunk, buf = entries of a row's candidate buffer for this handle's topk.
+ * GW_ERR_STATE for a host handle.                                             */
+int gw_knn_tiles(const gw_knn* m, int32_t* tq, int32_t* tc, int32_t* kc, int32_t* buf);
+/* Measurement aid (tools/bench_knn.py): the fp64 fma rate of this GPU under
+ * the main loop's instruction mix at its best - `blocks` workgroups of 256
+ * lanes, 16 independent fma chains per lane, `iters` rounds; one warm-up
+ * launch, one timed with device events.  GW_ERR_STATE for a host handle.      */
+int gw_knn_fma_rate(gw_knn* m, int blocks, int iters, double* fma_per_second);
+/* preprocess_simrank (DeepSim/src/main.py:132-167) on top-k rows: for
+ * t = 1 .. topk, acc[t-1] = the share, among the first min(t, listed)
+ * neighbours of every row, of those that have a label in common with the
+ * row's vertex (0 / 0 -> 0).  ids: [nrows][topk], -1 padded; row_ids: the
+ * vertex of each row (NULL: row r is vertex r); lab_off / lab_ids: CSR of the
+ * labels of the n vertices, ids ascending within a vertex.  Host code.  An id
+ * outside [-1, n) gives GW_ERR_RANGE.                                         */
+int gw_topk_label_agreement(const int32_t* ids, int64_t nrows, int topk, const int32_t* row_ids,
+                            const int64_t* lab_off, const int32_t* lab_ids, int64_t n, double* acc);
+
 /* ---- multi-GPU exchange (RCCL over xGMI) ---------------------------------- */
 /* the graph is replicated and units (walks, TopSim sources) are
  * sharded by global index with no data-path collective; the only exchange is
