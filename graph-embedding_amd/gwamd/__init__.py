@@ -17,6 +17,9 @@ Host-side mirror of the reference interfaces over the libgraphwalk C ABI
                       cosine / dot neighbours of the device-resident embedding, in gw_topsim's
                       row layout; label_agreement (preprocess_simrank);
                       `python -m gwamd.neighbors --emb X --output X.nn`
+* `gwamd.eigenmaps` — IsoMap_LE/simRank.py learn_embeddings (Laplacian eigenmaps of SimRank top-k
+                      rows, or of a graph's adjacency), sparse and symmetrised, in fp64;
+                      `python -m gwamd.eigenmaps --simrank X.sim.txt --output X.emb`
 * `gwamd.topsim`    — DeepSim/TopSimAll structures.Graph, TopSim_singleSample,
                       TopSim_Enumerate, SingleRandomWalk, SimRank (naive),
                       Print.printByOrder/printByOrderAll,

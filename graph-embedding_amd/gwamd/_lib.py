@@ -157,6 +157,31 @@ class KnnParams(ctypes.Structure):
         super().__init__(ctypes.sizeof(KnnParams), dim, topk, metric)
 
 
+LE_SYM_MEAN = 0
+LE_SYM_MAX = 1
+LE_CONVERGED = 0
+LE_NOT_CONVERGED = 1
+
+
+class LeParams(ctypes.Structure):
+    """gw_le_params_t (include/graphwalk.h); struct_size is filled in by default; block 0 = dim + 32."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("dim", ctypes.c_int32), ("block", ctypes.c_int32),
+                ("cheb_degree", ctypes.c_int32), ("max_iters", ctypes.c_int32), ("symmetrize", ctypes.c_int32),
+                ("tol", ctypes.c_double), ("min_eigenvalue", ctypes.c_double), ("seed", ctypes.c_uint64)]
+
+    def __init__(self, dim=128, block=0, cheb_degree=20, max_iters=100, symmetrize=LE_SYM_MEAN, tol=1e-8,
+                 min_eigenvalue=1e-5, seed=0):
+        super().__init__(ctypes.sizeof(LeParams), dim, block, cheb_degree, max_iters, symmetrize, tol, min_eigenvalue,
+                         seed)
+
+
+class LeStats(ctypes.Structure):
+    """gw_le_stats_t."""
+    _fields_ = [("state", ctypes.c_int32), ("iters", ctypes.c_int32), ("applies", ctypes.c_int64),
+                ("skipped", ctypes.c_int32), ("block_used", ctypes.c_int32), ("isolated", ctypes.c_int64),
+                ("max_residual", ctypes.c_double)]
+
+
 P = ctypes.c_void_p
 I32 = ctypes.c_int32
 I64 = ctypes.c_int64
@@ -269,6 +294,18 @@ SIGNATURES = {
     "gw_knn_tiles": (ctypes.c_int, [P, PI32, PI32, PI32, PI32]),
     "gw_knn_fma_rate": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, PD]),
     "gw_topk_label_agreement": (ctypes.c_int, [P, I64, ctypes.c_int, P, P, P, I64, P]),
+    "gw_le_create": (ctypes.c_int, [ctypes.c_int, I64, ctypes.POINTER(LeParams), PP]),
+    "gw_le_free": (ctypes.c_int, [P]),
+    "gw_le_last_error": (CP, [P]),
+    "gw_le_set_rows": (ctypes.c_int, [P, P, P, ctypes.c_int]),
+    "gw_le_set_csr": (ctypes.c_int, [P, P, P, P]),
+    "gw_le_solve": (ctypes.c_int, [P, ctypes.POINTER(LeStats), P]),
+    "gw_le_export": (ctypes.c_int, [P, P, P, P]),
+    "gw_le_vectors_dev": (ctypes.c_int, [P, PP, PI64]),
+    "gw_le_apply": (ctypes.c_int, [P, P, P, ctypes.c_int]),
+    "gw_le_tiles": (ctypes.c_int, [P, PI32, PI32, PI32]),
+    "gw_le_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
+    "gw_le_time_kernel": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, PD]),
     "gw_comm_unique_id": (ctypes.c_int, [P]),
     "gw_comm_init": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, PP]),
     "gw_comm_allgather": (ctypes.c_int, [P, P, P, I64, ctypes.c_int, P]),
@@ -296,13 +333,15 @@ def lib():
     return _lib
 
 
-def check(rc, handle=None, sgns=None, deepsim=None, ovr=None, knn=None):
+def check(rc, handle=None, sgns=None, deepsim=None, ovr=None, knn=None, le=None):
     """Raise for a failing status; `handle` a gw_graph, `sgns` a gw_sgns, `deepsim` a gw_deepsim or True for a
-    handle-less gw_deepsim call, `ovr` and `knn` likewise for gw_ovr and gw_knn (for the message)."""
+    handle-less gw_deepsim call, `ovr`, `knn` and `le` likewise for gw_ovr, gw_knn and gw_le (for the message)."""
     if rc == GW_OK:
         return
     L = lib()
-    if knn is not None:
+    if le is not None:
+        msg = L.gw_le_last_error(None if le is True else le)
+    elif knn is not None:
         msg = L.gw_knn_last_error(None if knn is True else knn)
     elif ovr is not None:
         msg = L.gw_ovr_last_error(None if ovr is True else ovr)

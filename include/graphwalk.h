@@ -850,6 +850,92 @@ int gw_knn_fma_rate(gw_knn* m, int blocks, int iters, double* fma_per_second);
 int gw_topk_label_agreement(const int32_t* ids, int64_t nrows, int topk, const int32_t* row_ids,
                             const int64_t* lab_off, const int32_t* lab_ids, int64_t n, double* acc);
 
+/* ---- Laplacian eigenmaps of top-k rows ---------------------------------------- */
+/* Replaces IsoMap_LE/simRank.py:95-123 (general form IsoMap_LE/LE.py:35-51): the
+ * eigenvectors of D^-1 L, L = D - W, for the smallest eigenvalues above
+ * min_eigenvalue, W built from top-k rows (gw_topsim's / gw_knn_query's layout)
+ * or from a CSR.  The reference forms W and D densely and calls np.linalg.eig;
+ * here W is sparse, symmetrised, and the pairs come from Chebyshev-filtered
+ * block subspace iteration on S = D^-1/2 W D^-1/2 (D^-1 L f = lambda f  <=>
+ * S u = (1 - lambda) u, f = s o u, s_i = 1 / sqrt(d_i)).  csrc/gw_le_law.h holds
+ * the one definition kernels and host evaluation (device = -1) share; every sum
+ * has one order, so the two agree bit for bit (tested).  All arithmetic is fp64.
+ *   input     an entry with id -1 ends its row; an id equal to the row and a
+ *             score that is NaN or <= 0 are dropped; of the entries that remain
+ *             a repeated id keeps the last value; an id outside [-1, n) gives
+ *             GW_ERR_RANGE;
+ *   W         w_ij = (a_ij + a_ji) / 2 (GW_LE_SYM_MEAN) or max(a_ij, a_ji)
+ *             (GW_LE_SYM_MAX): the reference uses the asymmetric matrix as it is;
+ *   isolated  a row with d_i = 0 is left out of the spectrum and its output row
+ *             is all zeros (the reference gives it D_ii = 1e-6);
+ *   output    eigenvalues ascending; f_c = s o u_c scaled to unit 2-norm, the
+ *             entry of largest magnitude positive (lowest row wins ties); the
+ *             fp32 copy is the fp64 one rounded once.
+ * Limits: n < 2^31; device path block <= 256 (GW_ERR_UNSUPPORTED); dim < block. */
+#define GW_LE_SYM_MEAN 0
+#define GW_LE_SYM_MAX 1
+#define GW_LE_CONVERGED 0
+#define GW_LE_NOT_CONVERGED 1 /* max_iters reached: the output is the last iterate */
+typedef struct gw_le gw_le;
+typedef struct gw_le_params_t {
+  int32_t struct_size;   /* as gw_sgns_params_t.struct_size                    */
+  int32_t dim;           /* eigenpairs returned (128)                          */
+  int32_t block;         /* width of the iterated block (0: dim + 32), clamped
+                            to the number of non-isolated rows                 */
+  int32_t cheb_degree;   /* operator applications per filter (20)              */
+  int32_t max_iters;     /* Rayleigh-Ritz steps (100)                          */
+  int32_t symmetrize;    /* GW_LE_SYM_MEAN (default) or GW_LE_SYM_MAX          */
+  double tol;            /* residual ||S u - theta u||_2 of every kept pair (1e-8) */
+  double min_eigenvalue; /* leading eigenvalues <= this are skipped (1e-5,
+                            LE.py:74; simRank.py:137 uses 1e-2)                */
+  uint64_t seed;         /* of the Philox start block                          */
+} gw_le_params_t;
+typedef struct gw_le_stats_t {
+  int32_t state;       /* GW_LE_CONVERGED / GW_LE_NOT_CONVERGED                */
+  int32_t iters;       /* Rayleigh-Ritz steps taken                            */
+  int64_t applies;     /* applications of S to the block                       */
+  int32_t skipped;     /* leading eigenvalues <= min_eigenvalue                */
+  int32_t block_used;  /* block after clamping                                 */
+  int64_t isolated;    /* rows with d_i = 0                                    */
+  double max_residual; /* over the skipped and the returned pairs              */
+} gw_le_stats_t;
+/* device >= 0: a GPU; -1: the host evaluation.  n = rows = vertices            */
+int gw_le_create(int device, int64_t n, const gw_le_params_t* params, gw_le** out);
+int gw_le_free(gw_le* m);
+const char* gw_le_last_error(const gw_le* m);
+/* W from rows (ids[n][topk] int32, scores[n][topk] double, row r = vertex r) or
+ * from a CSR (offsets[n + 1] int64, nbrs int32, weights double or NULL = 1.0).
+ * Host pointers in both modes: the operator is validated and assembled on the
+ * host and, for device >= 0, uploaded.                                          */
+int gw_le_set_rows(gw_le* m, const int32_t* ids, const double* scores, int topk);
+int gw_le_set_csr(gw_le* m, const int64_t* offsets, const int32_t* nbrs, const double* weights);
+/* Runs the solver on `stream` and synchronises it.  GW_ERR_STATE before set_*;
+ * GW_ERR_CAPACITY when the block cannot hold the skipped pairs, dim and one
+ * more (the message names the block needed) or the graph has fewer pairs above
+ * min_eigenvalue than dim.  stats is optional.  GW_LE_NOT_CONVERGED is a state,
+ * not an error.                                                               */
+int gw_le_solve(gw_le* m, gw_le_stats_t* stats, void* stream);
+/* Host arrays, each optional: eigenvalues[dim], vectors[n][dim], residuals[dim] */
+int gw_le_export(gw_le* m, double* eigenvalues, double* vectors, double* residuals);
+/* The fp32 vectors [n][dim] where they lie (device memory for device >= 0), for
+ * gw_knn_set_vectors / gw_ovr_set_features; valid until the next solve or free. */
+int gw_le_vectors_dev(gw_le* m, float** ptr, int64_t* pitch);
+/* y = S x for a caller's block [n][cols], row-major; device pointers for
+ * device >= 0, host pointers for -1.  x and y must not overlap.  Synchronous.   */
+int gw_le_apply(gw_le* m, const double* x, double* y, int cols);
+/* Launch geometry (tests place their shapes on its edges): rows of S per
+ * workgroup of k_le_apply, the law's row chunk GW_LE_CHUNK of the tall-skinny
+ * products, columns per lane pass of k_le_apply.  Valid for host handles too.  */
+int gw_le_tiles(const gw_le* m, int32_t* rows_per_wg, int32_t* chunk, int32_t* cols_per_pass);
+/* As gw_ovr_kernel_attrs                                                      */
+int gw_le_kernel_attrs(gw_le* m, int cap, const char** names, int32_t* vgprs, int32_t* scratch_bytes,
+                       int32_t* lds_bytes, int32_t* count);
+/* Measurement aid (tools/bench_le.py): times `reps` launches of one kernel on
+ * the solver's own buffers with device events; which: 0 apply (Chebyshev
+ * combine), 1 gram + reduce, 2 rotate.  After gw_le_solve; the blocks are
+ * overwritten, the exported results are not.  ms = mean per launch.           */
+int gw_le_time_kernel(gw_le* m, int which, int reps, double* ms);
+
 /* ---- multi-GPU exchange (RCCL over xGMI) ---------------------------------- */
 /* the graph is replicated and units (walks, TopSim sources) are
  * sharded by global index with no data-path collective; the only exchange is
