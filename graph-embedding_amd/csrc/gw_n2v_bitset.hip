@@ -770,7 +770,12 @@ __device__ __forceinline__ uint4 coop_piece(uint64_t sec, int lane, int j) {
   const uint64_t sj = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(sec >> 32), src, 64) << 32) |
                       (uint32_t)__shfl((int)(uint32_t)sec, src, 64);
   uint4 r = make_uint4(0u, 0u, 0u, 0u);
-  if (sj != 0ull) r = reinterpret_cast<const uint4*>(sj)[lane & 3];
+  // the address is rebuilt from integers: name its address space, or the load is a flat one
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  if (sj != 0ull) {
+    const u32x4 v = reinterpret_cast<const __attribute__((address_space(1))) u32x4*>(sj)[lane & 3];
+    r = make_uint4(v.x, v.y, v.z, v.w);
+  }
   return r;
 }
 
@@ -841,8 +846,15 @@ k_walk_bitset(gw_dev_graph G, BsParams P, int L, int64_t walk_begin, int64_t wal
       dg_act += active ? 1u : 0u;
     }
     uint32_t slot = 0xFFFFFFFFu;  // entry to fetch (accepted or speculative step)
-    bool spec = false;            // slot is accepted unless bit sbit of sw is set
-    uint32_t sw = 0u, sbit = 0u;
+    bool spec = false;            // slot is accepted unless bit sbit of the membership word is set
+    uint32_t sbit = 0u;
+    // The divergent part below only computes addresses; every global load of
+    // the iteration is issued after it, in straight-line code, into registers
+    // nothing else writes.  A lane reads at most one region word pair: its
+    // membership word (spec) or directory entries g, g+1 (dirld; g+1 only
+    // when it exists: dirnx).
+    const uint32_t* wa = nullptr;
+    bool dirld = false, dirnx = false;
     uint64_t sec = 0ull;  // 64 B sector this lane fetches: its next entry or a region block
     bool isblk = false;
     bool virt = false;    // return whose entry is already known (no fetch)
@@ -862,8 +874,9 @@ k_walk_bitset(gw_dev_graph G, BsParams P, int L, int64_t walk_begin, int64_t wal
         const uint32_t lo = dw0, hi = g + 1 < ndir ? dw1 : c;
         if (t < lo || t >= hi) {
           g += t < lo ? -1 : 1;
-          dw0 = hreg[g];
-          dw1 = g + 1 < ndir ? hreg[g + 1] : 0u;
+          wa = hreg + g;
+          dirld = true;
+          dirnx = g + 1 < ndir;
         } else {
           t -= lo;
           ph = 2;
@@ -945,8 +958,9 @@ k_walk_bitset(gw_dev_graph G, BsParams P, int L, int64_t walk_begin, int64_t wal
             if (ndir > kPDir) {  // directory in the region: guess the block, verify next iteration
               g = (int64_t)((float)j * (float)ndir * __builtin_amdgcn_rcpf((float)c));
               if (g >= ndir) g = ndir - 1;
-              dw0 = hreg[g];
-              dw1 = g + 1 < ndir ? hreg[g + 1] : 0u;
+              wa = hreg + g;
+              dirld = true;
+              dirnx = g + 1 < ndir;
               t = j;
               ph = 1;
             } else {  // <= 8 directory counts (u16) in w[1..4]: count those <= j
@@ -972,8 +986,8 @@ k_walk_bitset(gw_dev_graph G, BsParams P, int L, int64_t walk_begin, int64_t wal
             common = ef_mem && ef_bucket_has(pl, efU, (uint32_t)efl, es, es - eh, (uint32_t)k, win);
           } else if (k != (int64_t)kp && trial < (1u << 24)) {  // BS_REGION
             if (win & 1u) {  // the draw filter says maybe common: read the word
-              sw = (kGwDiag && (P.diag & 8)) ? G.bs_region[((uint32_t)k >> 5) & 0xFFFFu]  // timing experiment: no TLB misses
-                                : hreg[(meta >> 16) * kBlk + (k >> 5)];
+              wa = (kGwDiag && (P.diag & 8)) ? G.bs_region + (((uint32_t)k >> 5) & 0xFFFFu)  // timing experiment: no TLB misses
+                                : hreg + ((meta >> 16) * kBlk + (k >> 5));
               sbit = (uint32_t)(k & 31);
               spec = true;
             }
@@ -998,14 +1012,14 @@ k_walk_bitset(gw_dev_graph G, BsParams P, int L, int64_t walk_begin, int64_t wal
         }
       }
     }
-    // cooperative sector load (entries and region blocks alike): all four
-    // rounds in flight, then the exchange
+    // The iteration's one issue point: the per-lane region words, then the
+    // cooperative sector load (entries and region blocks alike), all in
+    // flight together; nothing is consumed before the exchange
+    uint32_t la = 0u, lb = 0u;
+    if (wa) la = wa[0];
+    if (dirnx) lb = wa[1];
     const uint4 r0 = coop_piece(sec, lane, 0), r1 = coop_piece(sec, lane, 1);
     const uint4 r2 = coop_piece(sec, lane, 2), r3 = coop_piece(sec, lane, 3);
-    if (spec && ((sw >> sbit) & 1u)) {  // the candidate was common: rejected
-      slot = 0xFFFFFFFFu;
-      sec = 0ull;
-    }
     // piece-major exchange: quarter q moves piece q (16 B) of EVERY walker —
     // the lanes that loaded it write their four rounds, then every lane reads
     // its own piece — so each lane's 16 words arrive unconditionally (no
@@ -1028,6 +1042,11 @@ k_walk_bitset(gw_dev_graph G, BsParams P, int L, int64_t walk_begin, int64_t wal
       E[4 * q + 3] = v.w;
     }
     __builtin_amdgcn_wave_barrier();
+    if (spec && ((la >> sbit) & 1u)) slot = 0xFFFFFFFFu;  // the candidate was common: rejected
+    // directory entries for the next iteration's ph 1 test; a lane that
+    // loaded none keeps its own
+    dw0 = dirld ? la : dw0;
+    dw1 = dirld ? lb : dw1;
     if (isblk) {  // the region block: pick the t-th set bit now
       kb = (uint32_t)(g * kDirBits) + (uint32_t)regs_select<kBlk>(E, t);
       ph = 3;
