@@ -316,6 +316,8 @@ int gw_n2v_prepare(gw_graph* g, double p, double q, int mode) {
 int gw_n2v_export_alias(const gw_graph* g_, int32_t* node_J, double* node_q, int64_t* edge_off,
                         int32_t* edge_J, double* edge_q);
 
+int gw_n2v_export_bitset(const gw_graph* g_, void* entries, uint32_t* region);  // gw_n2v_bitset.hip
+
 int gw_alias_setup(int device, const double* probs, int64_t K, int64_t* J, double* q) {
   if (K < 0 || (K > 0 && (!probs || !J || !q))) return gw_fail(nullptr, GW_ERR_INVALID, "bad arrays");
   std::string err;

@@ -166,7 +166,8 @@ __device__ __forceinline__ int bs_mode(uint32_t c, uint32_t d) {
 
 // Return elision (k_walk_bitset).  When both directed slots of an edge have
 // small common sets (c(u -> x) <= kDualC and c(x -> u) <= kDualC, both
-// degrees < 65536), the builder writes E(u -> x) as a DUAL list entry: its
+// degrees < 65536, u != x: a self-loop slot is its own reverse and stays a
+// plain list), the builder writes E(u -> x) as a DUAL list entry: its
 // own positions in N(x) in payload halfwords 0..5, the positions in N(u) of
 // the reverse slot's common set (the payload of E(x -> u)) in halfwords 6..11,
 // meta = kMetaDual | c(x -> u) << 2 (mode LIST).  Arriving through it, the
@@ -1625,6 +1626,22 @@ int gw_dev_bitset_build(gw_graph* g, int64_t budget_bytes, bool lists_only) {
 #undef BS_TRY
   cleanup();
   g->bitset_words = (int64_t)words;
+  return GW_OK;
+}
+
+// Read-only copy of the resident tables (tests decode them field by field):
+// entries = bs_nbr [nnz x 64 B]; region (optional) = bs_region, bitset_words
+// words (the one placeholder word of a lists-only build included).
+extern "C" int gw_n2v_export_bitset(const gw_graph* gc, void* entries, uint32_t* region) {
+  gw_graph* g = const_cast<gw_graph*>(gc);
+  if (!g) return gw_fail(nullptr, GW_ERR_INVALID, "NULL handle");
+  GW_GUARD_DEVICE(g, g->device);  // restores the caller's current device on return
+  if (!g->n2v_prepared || !g->d.bs_nbr)
+    return gw_fail(g, GW_ERR_STATE, "no bitset tables resident (GW_N2V_BITSET, or GW_N2V_REJECTION with listed entries)");
+  if (!entries) return gw_fail(g, GW_ERR_INVALID, "NULL entries");
+  GW_HIP_TRY(hipMemcpy(entries, g->d.bs_nbr, sizeof(gw_bs_nbr) * (size_t)g->nnz, hipMemcpyDeviceToHost));
+  if (region && g->d.bs_region)
+    GW_HIP_TRY(hipMemcpy(region, g->d.bs_region, sizeof(uint32_t) * (size_t)g->bitset_words, hipMemcpyDeviceToHost));
   return GW_OK;
 }
 

@@ -213,6 +213,7 @@ SIGNATURES = {
     "gw_graph_to_device": (ctypes.c_int, [P, ctypes.c_int]),
     "gw_n2v_prepare": (ctypes.c_int, [P, D, D, ctypes.c_int]),
     "gw_n2v_export_alias": (ctypes.c_int, [P, P, P, P, P, P]),
+    "gw_n2v_export_bitset": (ctypes.c_int, [P, P, P]),
     "gw_alias_setup": (ctypes.c_int, [ctypes.c_int, P, I64, P, P]),
     "gw_n2v_walks_replay": (ctypes.c_int, [P, ctypes.c_int, I64, P, P, I64, P, P, PI64]),
     "gw_n2v_walks": (ctypes.c_int, [P, ctypes.c_int, U64, I64, I64, ctypes.c_int, P, P, P, P]),

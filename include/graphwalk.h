@@ -241,6 +241,14 @@ int gw_n2v_prepare(gw_graph* g, double p, double q, int mode);
  * [edge_alias_entries] (REPLAY only; pass NULL to skip).                    */
 int gw_n2v_export_alias(const gw_graph* g, int32_t* node_J, double* node_q,
                         int64_t* edge_off, int32_t* edge_J, double* edge_q);
+/* Copy the per-slot tables of GW_N2V_BITSET, or of GW_N2V_REJECTION's listed
+ * entries, back to host memory, unchanged (for tests that decode them):
+ * entries [nnz x 64 B] in CSR slot order; region (NULL to skip) the region
+ * pool, (sampler_bytes - 64 nnz) / 4 words in GW_N2V_BITSET mode, the one
+ * placeholder word of a listed build.  GW_ERR_STATE when no such tables are
+ * resident (not prepared, REPLAY, rejection without listed entries, p = q = 1,
+ * weighted or directed graphs).                                             */
+int gw_n2v_export_bitset(const gw_graph* g, void* entries, uint32_t* region);
 /* Standalone alias_setup (node2vec.py:116-147) of one distribution on the
  * GPU: J[K], q[K] (J as int64 like np.int).                                 */
 int gw_alias_setup(int device, const double* probs, int64_t K, int64_t* J,

@@ -7,7 +7,8 @@ both ends from inv = 2^32 / d in double precision plus one integer correction
 instead of two 64-bit divisions.  This restates that computation (IEEE double,
 truncation like the C cast) and checks it against exact integer arithmetic on
 random and extreme (k, d); the GPU side is covered by the walk-parity tests,
-which read the filters.
+which read the filters, and by test_bitset_tables_gpu.py, which compares every
+exported filter word with the exact bucket set (a spurious bit included).
 """
 import numpy as np
 
