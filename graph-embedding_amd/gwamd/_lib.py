@@ -122,6 +122,24 @@ class DeepSimParams(ctypes.Structure):
                          beta1, beta2, epsilon, score_scale, seed)
 
 
+class SdneParams(ctypes.Structure):
+    """gw_sdne_params_t (include/graphwalk.h); struct_size is filled in by default; units = (u0, u1, u2, u3[, u4])."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("units", ctypes.c_int32 * 5), ("batch", ctypes.c_int32),
+                ("reserved0", ctypes.c_int32), ("learning_rate", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("epsilon", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("kl_weight", ctypes.c_double), ("kl_target", ctypes.c_double), ("seed", ctypes.c_uint64)]
+
+    def __init__(self, units=(0, 400, 100, 300), batch=100, learning_rate=0.01, beta1=0.9, beta2=0.999, epsilon=1e-8,
+                 weight_decay=0.1, kl_weight=0.1, kl_target=0.005, seed=0):
+        u = [int(x) for x in units]
+        if len(u) == 4:
+            u.append(u[0])
+        if len(u) != 5:
+            raise ValueError("units must be (u0, u1, u2, u3) or (u0, u1, u2, u3, u4)")
+        super().__init__(ctypes.sizeof(SdneParams), (ctypes.c_int32 * 5)(*u), batch, 0, learning_rate, beta1, beta2,
+                         epsilon, weight_decay, kl_weight, kl_target, seed)
+
+
 OVR_CONST_NEG = 0
 OVR_CONST_POS = 1
 OVR_FITTED = 2
@@ -274,6 +292,17 @@ SIGNATURES = {
     "gw_deepsim_vectors_dev": (ctypes.c_int, [P, PP, PI64]),
     "gw_deepsim_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
     "gw_write_deepsim_text": (ctypes.c_int, [CP, P, I64, ctypes.c_int]),
+    "gw_sdne_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(SdneParams), PP]),
+    "gw_sdne_free": (ctypes.c_int, [P]),
+    "gw_sdne_last_error": (CP, [P]),
+    "gw_sdne_set_rows_dense": (ctypes.c_int, [P, P, I64, I64]),
+    "gw_sdne_set_rows_csr": (ctypes.c_int, [P, P, P, P, I64]),
+    "gw_sdne_train": (ctypes.c_int, [P, I64, I64, P, P]),
+    "gw_sdne_gradients": (ctypes.c_int, [P, I64, PP]),
+    "gw_sdne_encode": (ctypes.c_int, [P, I64, I64, P]),
+    "gw_sdne_export": (ctypes.c_int, [P, PP, PP, PP]),
+    "gw_sdne_vectors_dev": (ctypes.c_int, [P, PP, PI64]),
+    "gw_sdne_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
     "gw_ovr_create": (ctypes.c_int, [ctypes.c_int, I64, ctypes.POINTER(OvrParams), PP]),
     "gw_ovr_free": (ctypes.c_int, [P]),
     "gw_ovr_last_error": (CP, [P]),
@@ -334,13 +363,16 @@ def lib():
     return _lib
 
 
-def check(rc, handle=None, sgns=None, deepsim=None, ovr=None, knn=None, le=None):
+def check(rc, handle=None, sgns=None, deepsim=None, ovr=None, knn=None, le=None, sdne=None):
     """Raise for a failing status; `handle` a gw_graph, `sgns` a gw_sgns, `deepsim` a gw_deepsim or True for a
-    handle-less gw_deepsim call, `ovr`, `knn` and `le` likewise for gw_ovr, gw_knn and gw_le (for the message)."""
+    handle-less gw_deepsim call, `ovr`, `knn`, `le` and `sdne` likewise for gw_ovr, gw_knn, gw_le and gw_sdne (for
+    the message)."""
     if rc == GW_OK:
         return
     L = lib()
-    if le is not None:
+    if sdne is not None:
+        msg = L.gw_sdne_last_error(None if sdne is True else sdne)
+    elif le is not None:
         msg = L.gw_le_last_error(None if le is True else le)
     elif knn is not None:
         msg = L.gw_knn_last_error(None if knn is True else knn)

@@ -673,6 +673,80 @@ int gw_deepsim_kernel_attrs(gw_deepsim* m, int cap, const char** names, int32_t*
  * 1e-4 <= |x| < 1e16, else scientific with a two-digit exponent).             */
 int gw_write_deepsim_text(const char* path, const float* w1, int64_t n, int dim);
 
+/* ---- embeddings: SDNE (four-layer dense autoencoder) -------------------------- */
+/* Replaces SDNE (SDNE/SDNE.py:66-176).  units = {u0, u1, u2, u3, u4}, u4 = u0;
+ * rows of width u0, dense or sparse (a graph's adjacency, top-k rows):
+ *   h1 = relu(x . w1 + b1), z2 = h1 . w2 + b2 (the embedding, before the relu),
+ *   h2 = relu(z2), h3 = relu(h2 . w3 + b3), y = h3 . w4 + b4,
+ *   loss = sum((y - x)^2) / 2 / batch + weight_decay * sum_theta sum(theta^2) / 2
+ *          + kl_weight * KL(kl_target || mean(h2)),
+ * TF1 Adam (lr_t as gw_deepsim) dense over all eight tensors.  Step t trains on
+ * rows [(t mod nb) * batch, +batch), nb = floor(N / batch): the last N mod batch
+ * rows are never trained on but are encoded.  The first-order proximity term
+ * of the reference's docstring (not coded there) and the SDNE paper's weighting
+ * of nonzero entries are not built.
+ * csrc/gw_sdne_law.h holds the one definition (float order, draws) that the
+ * kernels and the host evaluation (device = -1) share; they agree bit for bit
+ * (tested).  Every product reduces in chunks of 128 along its reduction index:
+ * an fmaf chain per chunk (chunk 0 from the bias, or +0 backward), the chunks
+ * added in ascending order.  Philox4x32-10 keying as gw_deepsim:
+ *   initial  tag "sdI0": counter (index low, index high, tensor, attempt),
+ *            tensor 0, 2, 4, 6 = w1..w4; truncated normal, stddev 0.1.
+ * Device path: u1, u2, u3 <= 1024 and batch <= 128 (else GW_ERR_UNSUPPORTED);
+ * u0 is bounded by memory; the host path takes any positive values.  HBM:
+ * 12 bytes per parameter (value and Adam moments), 12 * batch * (u0 + u1 + u2
+ * + u3) of activations and their gradients, 4 * ceil(u0 / 128) * batch *
+ * max(u1, u3) of chunk partials when u0 > 512, and 4 * N * u2 for the encoding. */
+typedef struct gw_sdne gw_sdne;
+typedef struct gw_sdne_params_t {
+  int32_t struct_size;  /* as gw_sgns_params_t.struct_size                        */
+  int32_t units[5];     /* {u0 (required), 400, 100, 300, u4 (0 = u0)}            */
+  int32_t batch;        /* 100                                                    */
+  int32_t reserved0;    /* 0                                                      */
+  double learning_rate; /* 0.01                                                   */
+  double beta1;         /* 0.9                                                    */
+  double beta2;         /* 0.999                                                  */
+  double epsilon;       /* 1e-8                                                   */
+  double weight_decay;  /* 0.1                                                    */
+  double kl_weight;     /* 0.1                                                    */
+  double kl_target;     /* 0.005 (p)                                              */
+  uint64_t seed;        /* 0                                                      */
+} gw_sdne_params_t;
+/* device >= 0: a GPU; -1: the host evaluation.  Initialises w1..w4 (biases and
+ * Adam state 0).  u4 != u0 gives GW_ERR_INVALID.                               */
+int gw_sdne_create(int device, const gw_sdne_params_t* params, gw_sdne** out);
+int gw_sdne_free(gw_sdne* m);
+const char* gw_sdne_last_error(const gw_sdne* m);
+/* The rows: a dense fp32 matrix, row r at rows + r * pitch floats (device
+ * memory for device >= 0).  It stays where it is and must outlive the calls
+ * that read it.  n < batch gives GW_ERR_INVALID.  Replaces earlier rows.       */
+int gw_sdne_set_rows_dense(gw_sdne* m, const float* rows, int64_t n, int64_t pitch);
+/* The rows as CSR (host pointers, copied): offsets[n + 1], cols, vals (NULL =
+ * 1).  A column outside [0, u0) gives GW_ERR_RANGE, a column twice in one row
+ * GW_ERR_INVALID, n < batch GW_ERR_INVALID.  Replaces earlier rows.            */
+int gw_sdne_set_rows_csr(gw_sdne* m, const int64_t* offsets, const int32_t* cols, const float* vals, int64_t n);
+/* Steps [step_begin, step_begin + step_count); pieces equal one call.
+ * loss_out[step_count] (host, optional): each step's loss before its update.
+ * Runs on `stream` and synchronises it.                                       */
+int gw_sdne_train(gw_sdne* m, int64_t step_begin, int64_t step_count, double* loss_out, void* stream);
+/* Gradient of step's batch at the current parameters (host copies, NULL
+ * skips), weight decay included: grads = {w1[u0*u1], b1[u1], w2[u1*u2], b2,
+ * w3[u2*u3], b3, w4[u3*u4], b4}.  Nothing is updated.                          */
+int gw_sdne_gradients(gw_sdne* m, int64_t step, float* const grads[8]);
+/* z2 of rows [row_begin, row_begin + row_count) of the current rows into the
+ * handle's [N][u2] matrix and, when out is not NULL, into out[row_count][u2]
+ * (host).                                                                      */
+int gw_sdne_encode(gw_sdne* m, int64_t row_begin, int64_t row_count, float* out);
+/* Host copies (NULL skips): par / adam_m / adam_v each in the order of
+ * gw_sdne_gradients.                                                           */
+int gw_sdne_export(gw_sdne* m, float* const par[8], float* const adam_m[8], float* const adam_v[8]);
+/* The encoded [N][u2] matrix where it lives (HBM for device >= 0), complete
+ * after an encode of all rows: row r at ptr + r * pitch floats.               */
+int gw_sdne_vectors_dev(gw_sdne* m, float** ptr, int64_t* pitch);
+/* As gw_deepsim_kernel_attrs.                                                  */
+int gw_sdne_kernel_attrs(gw_sdne* m, int cap, const char** names, int32_t* vgprs, int32_t* scratch_bytes,
+                         int32_t* lds_bytes, int32_t* count);
+
 /* ---- scoring: one-vs-rest logistic regression, top-k prediction, F1 ---------- */
 /* Replaces classify.scoring (node2vec/src/classify.py, DeepSim/src/classify.py):
  * TopKRanker(LogisticRegression(penalty='l2')) fitted one-vs-rest on a share of
