@@ -1,7 +1,8 @@
 // SDNE trainer kernels (gfx950): the training law of gw_sdne_law.h.
 //
 // One step is a fixed chain on the caller's stream, no host round trip:
-//   k_sdne_batch      the step's B rows as a dense x[B][u0] (dense input: copied; CSR: zeroed and scattered)
+//   k_sdne_batch      the step's B rows (gw_sdne_row: ordered or the epoch's permutation) as a dense x[B][u0]
+//                     (dense input: copied; CSR: zeroed and scattered) and their ids
 //   k_sdne_gemm       every product of the law on the fp32 MFMA (32x32x2, a k-ordered fmaf chain), operands
 //                     staged in LDS, 64x64 output tile per workgroup, general operand strides:
 //                       forward        z = in . W + b        (4 times; bias preload, relu, the pre-activation kept)
@@ -10,6 +11,8 @@
 //                     A product of at most kInKernelChunks chunks walks its chunks inside the kernel; a longer one
 //                     (the two that reduce over u0) runs one chunk per workgroup into `part` and
 //   k_sdne_reduce     adds the chunk partials in ascending order and applies the same epilogue
+//   k_sdne_first      with first_order > 0, after forward layer 2: g1[B][u2], the first-order term's gradient; one
+//                     workgroup per batch row, the nonzero S_ij compacted in j order into LDS, threads over c
 //   k_sdne_q          q = mean(h2) in the law's order and the KL gradient scalar
 //   k_sdne_loss_*     the reported loss in fp64 (only when it is asked for)
 //   k_sdne_bias       the four bias gradients and their Adam
@@ -28,6 +31,8 @@ struct gw_sdne_dev {
   gw_dev_buf<float> par[8], am[8], av[8];  // {w1, b1, .., w4, b4} and their Adam moments
   gw_dev_buf<float> grad[8];               // diagnostic, allocated by gw_sdne_gradients
   gw_dev_buf<float> x;                     // [B][u0]
+  gw_dev_buf<int64_t> rowid;               // [B]: the input row of each staged row
+  gw_dev_buf<float> g1;                    // [B][u2]: the first-order term's gradient (first_order > 0)
   gw_dev_buf<float> z[4], h[3];            // pre-activations z1, z2, z3, y; h1, h2, h3
   gw_dev_buf<float> dz[4];                 // dz1 .. dz4
   gw_dev_buf<float> part;                  // [chunks][M][N] of the longest split product
@@ -70,12 +75,13 @@ struct Epi {
   // EPI_FWD
   const float* bias;  // the chain's start
   float* pre;         // [M][N]
-  float* act;         // relu(z), or (z - xin) / Bf when xin is set; may be NULL
+  float* act;         // relu(z), or gw_sdne_dz4(z, xin, bw, Bf) when xin is set; may be NULL
   const float* xin;
-  float Bf;
+  float Bf, bw;
   // EPI_BWD
   const float* mask;  // pre-activation [M][N]
   const float* klg;   // NULL or the scalar added before the mask
+  const float* add;   // NULL or [M][N] added after the mask
   float* out;         // dz [M][N]; EPI_WGT with adam off: g [M][N]
   // EPI_WGT
   float *W, *am, *av;
@@ -90,15 +96,16 @@ __device__ __forceinline__ void apply_epi(const Epi& E, int row, int col, int N,
     E.pre[at] = v;
     if (E.act) {
       if (E.xin) {
-        const float d = v - E.xin[at];
-        E.act[at] = d / E.Bf;
+        E.act[at] = gw_sdne_dz4(v, E.xin[at], E.bw, E.Bf);
       } else {
         E.act[at] = v > 0.0f ? v : 0.0f;
       }
     }
   } else if (E.kind == EPI_BWD) {
     if (E.klg) v = v + *E.klg;
-    E.out[at] = E.mask[at] > 0.0f ? v : 0.0f;
+    v = E.mask[at] > 0.0f ? v : 0.0f;
+    if (E.add) v = v + E.add[at];
+    E.out[at] = v;
   } else {
     const float g = fmaf(E.wd, E.W[at], v);
     if (E.adam)
@@ -108,11 +115,22 @@ __device__ __forceinline__ void apply_epi(const Epi& E, int row, int col, int N,
   }
 }
 
+// which input rows a launch of k_sdne_batch stages: a step's (step = 1: gw_sdne_row of slot blockIdx.x) or
+// row0 + blockIdx.x (the encoder)
+struct RowSel {
+  int step, shuffle;
+  uint64_t seed, t;
+  int64_t N, B, row0;
+};
+
 __global__ __launch_bounds__(kThreads) void k_sdne_batch(float* __restrict__ x, int u0, const float* __restrict__ rows,
                                                          int64_t pitch, const int64_t* __restrict__ offs,
                                                          const int32_t* __restrict__ cols,
-                                                         const float* __restrict__ vals, int64_t row0) {
-  const int64_t r = row0 + blockIdx.x;
+                                                         const float* __restrict__ vals, const RowSel R,
+                                                         int64_t* __restrict__ rowid) {
+  const int64_t r = R.step ? gw_sdne_row(R.seed, R.shuffle, R.N, R.B, R.t, blockIdx.x) : R.row0 + blockIdx.x;
+  if (r < 0 || r >= R.N) return;  // cannot happen: the permutation maps [0, N) onto itself
+  if (threadIdx.x == 0) rowid[blockIdx.x] = r;
   float* xr = x + (int64_t)blockIdx.x * u0;
   if (rows) {
     for (int i = threadIdx.x; i < u0; i += kThreads) xr[i] = rows[r * pitch + i];
@@ -215,6 +233,59 @@ __global__ __launch_bounds__(kThreads) void k_sdne_reduce(const float* __restric
   apply_epi(E, (int)(o / N), (int)(o % N), N, acc);
 }
 
+// g1[i][c] = coef * (the chain over j ascending from +0 of fmaf(S_ij, z2[i][c] - z2[j][c], acc)), S_ij = a_ij + a_ji,
+// a_ij = x[i][rowid[j]].  Workgroup i: threads [0, B) form S_i., the nonzero ones are compacted in j order into LDS
+// (skipping S_ij = 0 keeps the bits, gw_sdne_law.h), then the threads run over c and read z2[j][.] coalesced.
+__global__ __launch_bounds__(kThreads) void k_sdne_first(const float* __restrict__ x, int u0,
+                                                         const int64_t* __restrict__ rowid,
+                                                         const float* __restrict__ z2, int B, int u2, float coef,
+                                                         float* __restrict__ g1) {
+  static_assert(GW_SDNE_MAX_BATCH <= kThreads && GW_SDNE_MAX_BATCH % 64 == 0, "one thread per batch row, whole waves");
+  constexpr int kW = GW_SDNE_MAX_BATCH / 64;
+  __shared__ float Sv[GW_SDNE_MAX_BATCH];
+  __shared__ int Sj[GW_SDNE_MAX_BATCH];
+  __shared__ int cnt[kW];
+  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  float s = 0.0f;
+  bool nz = false;
+  int before = 0;
+  if (tid < GW_SDNE_MAX_BATCH) {  // whole waves
+    if (tid < B) {
+      const int64_t ri = rowid[i], rj = rowid[tid];
+      if ((uint64_t)ri < (uint64_t)u0 && (uint64_t)rj < (uint64_t)u0) {  // N = u0 was checked when the rows were set
+        const float aij = x[(int64_t)i * u0 + rj];
+        const float aji = x[(int64_t)tid * u0 + ri];
+        s = aij + aji;
+        nz = s != 0.0f;
+      }
+    }
+    const unsigned long long mask = __ballot(nz);
+    before = __popcll(mask & ((1ull << lane) - 1ull));
+    if (lane == 0) cnt[wv] = __popcll(mask);
+  }
+  __syncthreads();
+  int n = 0;
+#pragma unroll
+  for (int w = 0; w < kW; ++w) {
+    if (w == wv && nz) {
+      Sv[n + before] = s;
+      Sj[n + before] = tid;
+    }
+    n += cnt[w];
+  }
+  __syncthreads();
+  for (int c = tid; c < u2; c += kThreads) {
+    const float zi = z2[(int64_t)i * u2 + c];
+    float acc = 0.0f;
+#pragma unroll 4
+    for (int k = 0; k < n; ++k) {
+      const float d = zi - z2[(int64_t)Sj[k] * u2 + c];
+      acc = fmaf(Sv[k], d, acc);
+    }
+    g1[(int64_t)i * u2 + c] = coef * acc;
+  }
+}
+
 // qk[0] = q, qk[1] = klg
 __global__ __launch_bounds__(GW_SDNE_MAX_BATCH) void k_sdne_q(const float* __restrict__ h2, int B, int u2, float p,
                                                                float klw, float* __restrict__ qk) {
@@ -269,17 +340,38 @@ struct LossArgs {
   int64_t nyx;
   const float* par[8];
   int64_t n[8];
+  double bw;
+  // the first-order term (z2 = NULL: none)
+  const float* z2;
+  const int64_t* rowid;
+  int B, u0, u2;
 };
 
-// lpart[2 * block] = the block's share of sum((y - x)^2), lpart[2 * block + 1] of sum(theta^2) (fp64)
+// lpart[3 * block + {0, 1, 2}] = the block's share of sum(w * (y - x)^2), of sum(theta^2) and of
+// sum(a_ij * |z2_i - z2_j|^2) (fp64)
 __global__ __launch_bounds__(kThreads) void k_sdne_loss_part(const LossArgs L, double* __restrict__ lpart) {
-  __shared__ double red[2][kThreads];
+  __shared__ double red[3][kThreads];
   const int64_t gid = (int64_t)blockIdx.x * kThreads + threadIdx.x, stride = (int64_t)gridDim.x * kThreads;
-  double rec = 0.0, reg = 0.0;
+  double rec = 0.0, reg = 0.0, l1 = 0.0;
   for (int64_t i = gid; i < L.nyx; i += stride) {
-    const double d = (double)L.y[i] - (double)L.x[i];
-    rec += d * d;
+    const float xv = L.x[i];
+    const double d = (double)L.y[i] - (double)xv;
+    rec += (xv != 0.0f ? L.bw : 1.0) * (d * d);
   }
+  if (L.z2)
+    for (int p = blockIdx.x; p < L.B * L.B; p += gridDim.x) {  // a pair (i, j) per trip, the threads over c
+      const int i = p / L.B, j = p % L.B;
+      const int64_t rj = L.rowid[j];
+      if ((uint64_t)rj >= (uint64_t)L.u0) continue;
+      const double a = (double)L.x[(int64_t)i * L.u0 + rj];
+      if (a == 0.0) continue;
+      double sq = 0.0;
+      for (int c = threadIdx.x; c < L.u2; c += kThreads) {
+        const double d = (double)L.z2[(int64_t)i * L.u2 + c] - (double)L.z2[(int64_t)j * L.u2 + c];
+        sq += d * d;
+      }
+      l1 += a * sq;
+    }
   for (int t = 0; t < 8; ++t)
     for (int64_t i = gid; i < L.n[t]; i += stride) {
       const double v = (double)L.par[t][i];
@@ -287,31 +379,35 @@ __global__ __launch_bounds__(kThreads) void k_sdne_loss_part(const LossArgs L, d
     }
   red[0][threadIdx.x] = rec;
   red[1][threadIdx.x] = reg;
+  red[2][threadIdx.x] = l1;
   __syncthreads();
   for (int s = kThreads / 2; s > 0; s >>= 1) {
     if ((int)threadIdx.x < s) {
       red[0][threadIdx.x] += red[0][threadIdx.x + s];
       red[1][threadIdx.x] += red[1][threadIdx.x + s];
+      red[2][threadIdx.x] += red[2][threadIdx.x + s];
     }
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    lpart[2 * blockIdx.x] = red[0][0];
-    lpart[2 * blockIdx.x + 1] = red[1][0];
+    lpart[3 * blockIdx.x] = red[0][0];
+    lpart[3 * blockIdx.x + 1] = red[1][0];
+    lpart[3 * blockIdx.x + 2] = red[2][0];
   }
 }
 
 __global__ void k_sdne_loss_final(const double* __restrict__ lpart, int nblocks, const float* __restrict__ qk, double p,
-                                  double klw, double wd, double B, double* __restrict__ out) {
+                                  double klw, double wd, double B, double alpha, double* __restrict__ out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double rec = 0.0, reg = 0.0;
+  double rec = 0.0, reg = 0.0, l1 = 0.0;
   for (int i = 0; i < nblocks; ++i) {
-    rec += lpart[2 * i];
-    reg += lpart[2 * i + 1];
+    rec += lpart[3 * i];
+    reg += lpart[3 * i + 1];
+    l1 += lpart[3 * i + 2];
   }
   const double q = (double)qk[0];
   const double kl = p * log(p / (q + 1e-8)) + (1.0 - p) * log((1.0 - p) / (1.0 - q + 1e-8));
-  *out = rec / 2.0 / B + wd * reg / 2.0 + klw * kl;
+  *out = rec / 2.0 / B + wd * reg / 2.0 + klw * kl + alpha / B * l1;
 }
 
 bool is_split(int K) { return gw_sdne_chunks(K) > kInKernelChunks; }
@@ -350,13 +446,20 @@ int launch_forward(gw_sdne* m, hipStream_t st, int l, int M, float* pre, bool wa
   E.act = !want_act ? nullptr : (l == 3 ? dv.dz[3].get() : dv.h[l].get());
   E.xin = l == 3 ? dv.x.get() : nullptr;
   E.Bf = (float)m->B;
+  const float bf = (float)m->p.nonzero_weight;
+  E.bw = bf * bf;
   return launch_gemm(m, st, G, E);
 }
 
-int launch_batch(gw_sdne* m, hipStream_t st, int64_t row0, int M) {
+// stage M rows: step t's batch (step = true, M = B) or rows [row0, row0 + M)
+int launch_batch(gw_sdne* m, hipStream_t st, bool step, uint64_t t, int64_t row0, int M) {
   gw_sdne_dev& dv = *m->dev;
+  RowSel R = {};
+  R.step = step, R.shuffle = m->p.shuffle;
+  R.seed = m->p.seed, R.t = t;
+  R.N = m->N, R.B = m->B, R.row0 = row0;
   k_sdne_batch<<<M, kThreads, 0, st>>>(dv.x.get(), m->u[0], m->sparse ? nullptr : m->rows, m->pitch, dv.offs.get(),
-                                       dv.cols.get(), dv.vals.get(), row0);
+                                       dv.cols.get(), dv.vals.get(), R, dv.rowid.get());
   return GW_OK;
 }
 
@@ -365,11 +468,16 @@ int launch_step(gw_sdne* m, uint64_t t, int adam, double* loss_dev, hipStream_t 
   gw_sdne_dev& dv = *m->dev;
   const int* u = m->u;
   const int B = m->B;
-  const int64_t nb = m->N / B;
+  const double alpha = m->p.first_order;
   const gw_sdne_adam_c C = gw_sdne_adam_consts(m->p.learning_rate, m->p.beta1, m->p.beta2, m->p.epsilon, t);
   const float wd = (float)m->p.weight_decay;
-  int rc = launch_batch(m, st, (int64_t)(t % (uint64_t)nb) * B, B);
-  for (int l = 0; l < 4 && rc == GW_OK; ++l) rc = launch_forward(m, st, l, B, nullptr, true);
+  int rc = launch_batch(m, st, true, t, 0, B);
+  for (int l = 0; l < 4 && rc == GW_OK; ++l) {
+    rc = launch_forward(m, st, l, B, nullptr, true);
+    if (l == 1 && rc == GW_OK && alpha > 0.0)
+      k_sdne_first<<<B, kThreads, 0, st>>>(dv.x.get(), u[0], dv.rowid.get(), dv.z[1].get(), B, u[2],
+                                           (float)(2.0 * alpha / (double)B), dv.g1.get());
+  }
   if (rc != GW_OK) return rc;
   k_sdne_q<<<1, GW_SDNE_MAX_BATCH, 0, st>>>(dv.h[1].get(), B, u[2], (float)m->p.kl_target, (float)m->p.kl_weight,
                                             dv.q.get());
@@ -382,9 +490,14 @@ int launch_step(gw_sdne* m, uint64_t t, int adam, double* loss_dev, hipStream_t 
       L.par[t8] = dv.par[t8].get();
       L.n[t8] = (int64_t)gw_sdne_numel(m, t8);
     }
+    const float bf = (float)m->p.nonzero_weight;
+    L.bw = (double)(bf * bf);
+    L.z2 = alpha > 0.0 ? dv.z[1].get() : nullptr;
+    L.rowid = dv.rowid.get();
+    L.B = B, L.u0 = u[0], L.u2 = u[2];
     k_sdne_loss_part<<<kLossBlocks, kThreads, 0, st>>>(L, dv.lpart.get());
     k_sdne_loss_final<<<1, 64, 0, st>>>(dv.lpart.get(), kLossBlocks, dv.q.get(), m->p.kl_target, m->p.kl_weight,
-                                        m->p.weight_decay, (double)B, loss_dev);
+                                        m->p.weight_decay, (double)B, alpha, loss_dev);
   }
   // backward data, layers 4 -> 2: dz_l = (dz_{l+1} . W_{l+1}^T [+ klg]) masked by z_l; all against the old weights
   for (int l = 3; l >= 1 && rc == GW_OK; --l) {
@@ -398,6 +511,7 @@ int launch_step(gw_sdne* m, uint64_t t, int adam, double* loss_dev, hipStream_t 
     E.kind = EPI_BWD;
     E.mask = dv.z[l - 1].get();
     E.klg = l == 2 ? dv.q.get() + 1 : nullptr;
+    E.add = l == 2 && alpha > 0.0 ? dv.g1.get() : nullptr;
     E.out = dv.dz[l - 1].get();
     rc = launch_gemm(m, st, G, E);
   }
@@ -452,6 +566,8 @@ int gw_sdne_dev_alloc(gw_sdne* m, const std::vector<float> init[8]) {
     if (e == hipSuccess) e = hipMemset(dv.av[t].get(), 0, n * sizeof(float));
   }
   if (e == hipSuccess) e = dv.x.alloc(B * u[0]);
+  if (e == hipSuccess) e = dv.rowid.alloc(B);
+  if (e == hipSuccess) e = dv.g1.alloc(B * u[2]);
   for (int l = 0; l < 4 && e == hipSuccess; ++l) {
     e = dv.z[l].alloc(B * u[l + 1]);
     if (e == hipSuccess) e = dv.dz[l].alloc(B * u[l + 1]);
@@ -466,7 +582,7 @@ int gw_sdne_dev_alloc(gw_sdne* m, const std::vector<float> init[8]) {
   }
   if (e == hipSuccess) e = dv.part.alloc(part);
   if (e == hipSuccess) e = dv.q.alloc(2);
-  if (e == hipSuccess) e = dv.lpart.alloc(2 * kLossBlocks);
+  if (e == hipSuccess) e = dv.lpart.alloc(3 * kLossBlocks);
   if (e != hipSuccess) return gw_sdne_fail(m, GW_ERR_NOMEM, "device allocation failed: %s", hipGetErrorString(e));
   return GW_OK;
 }
@@ -531,6 +647,16 @@ int gw_sdne_dev_gradients(gw_sdne* m, int64_t step, float* const grads[8]) {
   return GW_OK;
 }
 
+int gw_sdne_dev_batch_rows(gw_sdne* m, int64_t step, int64_t* rows) {
+  GW_DEV_GUARD(m);
+  GW_DEV_TRY(m, hipDeviceSynchronize());
+  launch_batch(m, nullptr, true, (uint64_t)step, 0, m->B);
+  GW_DEV_TRY(m, hipGetLastError());
+  GW_DEV_TRY(m, hipDeviceSynchronize());
+  GW_DEV_TRY(m, hipMemcpy(rows, m->dev->rowid.get(), (size_t)m->B * sizeof(int64_t), hipMemcpyDeviceToHost));
+  return GW_OK;
+}
+
 int gw_sdne_dev_encode(gw_sdne* m, int64_t row_begin, int64_t row_count, float* out) {
   GW_DEV_GUARD(m);
   gw_sdne_dev& dv = *m->dev;
@@ -538,7 +664,7 @@ int gw_sdne_dev_encode(gw_sdne* m, int64_t row_begin, int64_t row_count, float* 
   GW_DEV_TRY(m, hipDeviceSynchronize());  // the rows' producer and any training call are complete
   for (int64_t r0 = row_begin; r0 < end; r0 += m->B) {
     const int M = (int)std::min<int64_t>(m->B, end - r0);
-    int rc = launch_batch(m, nullptr, r0, M);
+    int rc = launch_batch(m, nullptr, false, 0, r0, M);
     if (rc == GW_OK) rc = launch_forward(m, nullptr, 0, M, nullptr, true);
     if (rc == GW_OK) rc = launch_forward(m, nullptr, 1, M, dv.enc.get() + r0 * u2, false);
     if (rc != GW_OK) return rc;
@@ -573,7 +699,7 @@ extern "C" int gw_sdne_kernel_attrs(gw_sdne* m, int cap, const char** names, int
       {"k_sdne_batch", (const void*)k_sdne_batch, 0},           {"k_sdne_gemm", (const void*)k_sdne_gemm, 0},
       {"k_sdne_reduce", (const void*)k_sdne_reduce, 0},         {"k_sdne_q", (const void*)k_sdne_q, 0},
       {"k_sdne_loss_part", (const void*)k_sdne_loss_part, 0},   {"k_sdne_loss_final", (const void*)k_sdne_loss_final, 0},
-      {"k_sdne_bias", (const void*)k_sdne_bias, 0}};
+      {"k_sdne_bias", (const void*)k_sdne_bias, 0},             {"k_sdne_first", (const void*)k_sdne_first, 0}};
   return gw_trainer_kernel_attrs(m, ks, cap, names, vgprs, scratch_bytes, lds_bytes, count);
 }
 

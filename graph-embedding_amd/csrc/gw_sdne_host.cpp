@@ -35,6 +35,7 @@ void gw_sdne_dev_free(gw_sdne*) {}
 int gw_sdne_dev_set_rows(gw_sdne* m) { return no_dev(m); }
 int gw_sdne_dev_train(gw_sdne* m, int64_t, int64_t, double*, void*) { return no_dev(m); }
 int gw_sdne_dev_gradients(gw_sdne* m, int64_t, float* const*) { return no_dev(m); }
+int gw_sdne_dev_batch_rows(gw_sdne* m, int64_t, int64_t*) { return no_dev(m); }
 int gw_sdne_dev_encode(gw_sdne* m, int64_t, int64_t, float*) { return no_dev(m); }
 int gw_sdne_dev_export(gw_sdne* m, float* const*, float* const*, float* const*) { return no_dev(m); }
 float* gw_sdne_dev_vectors(gw_sdne* m) { return no_dev(m), nullptr; }
@@ -58,6 +59,7 @@ extern "C" int gw_sdne_create(int device, const gw_sdne_params_t* params, gw_sdn
   p.weight_decay = 0.1;
   p.kl_weight = 0.1;
   p.kl_target = 0.005;
+  p.nonzero_weight = 1.0;
   if (params) {
     if (params->struct_size < (int32_t)sizeof(int32_t))
       return gw_sdne_fail(nullptr, GW_ERR_INVALID, "gw_sdne_params_t.struct_size %d", (int)params->struct_size);
@@ -75,6 +77,12 @@ extern "C" int gw_sdne_create(int device, const gw_sdne_params_t* params, gw_sdn
       !(p.beta2 >= 0.0 && p.beta2 < 1.0) || !(p.epsilon > 0.0) || !isfinite(p.weight_decay) || !isfinite(p.kl_weight) ||
       !(p.kl_target > 0.0 && p.kl_target < 1.0))
     return gw_sdne_fail(nullptr, GW_ERR_INVALID, "bad learning_rate / beta / epsilon / weight_decay / kl_weight / kl_target");
+  if (!isfinite(p.nonzero_weight) || !(p.nonzero_weight > 0.0))
+    return gw_sdne_fail(nullptr, GW_ERR_INVALID, "nonzero_weight %g must be finite and positive", p.nonzero_weight);
+  if (!isfinite(p.first_order) || !(p.first_order >= 0.0))
+    return gw_sdne_fail(nullptr, GW_ERR_INVALID, "first_order %g must be finite and not negative", p.first_order);
+  if (p.shuffle != 0 && p.shuffle != 1)
+    return gw_sdne_fail(nullptr, GW_ERR_INVALID, "shuffle %d must be 0 or 1", p.shuffle);
   if (device < -1) return gw_sdne_fail(nullptr, GW_ERR_INVALID, "device %d", device);
   if (device >= 0) {
     if (p.units[1] > GW_SDNE_MAX_HIDDEN || p.units[2] > GW_SDNE_MAX_HIDDEN || p.units[3] > GW_SDNE_MAX_HIDDEN)
@@ -134,10 +142,21 @@ static int rows_set(gw_sdne* m) {
   return GW_OK;
 }
 
+// the first-order term reads a_ij = x_i[row(j)]: the rows are a square matrix
+static bool square_ok(gw_sdne* m, int64_t n) {
+  if (!(m->p.first_order > 0.0) || n == m->u[0]) return true;
+  gw_sdne_fail(m, GW_ERR_INVALID,
+               "first_order > 0: the first-order term reads the adjacency, so the %lld rows must equal the row "
+               "width %d",
+               (long long)n, m->u[0]);
+  return false;
+}
+
 extern "C" int gw_sdne_set_rows_dense(gw_sdne* m, const float* rows, int64_t n, int64_t pitch) {
   if (!m) return gw_sdne_fail(nullptr, GW_ERR_INVALID, "NULL handle");
   if (!rows || n < 1 || pitch < m->u[0]) return gw_sdne_fail(m, GW_ERR_INVALID, "bad row arguments");
   if (n < m->B) return gw_sdne_fail(m, GW_ERR_INVALID, "%lld rows, fewer than the batch of %d", (long long)n, m->B);
+  if (!square_ok(m, n)) return GW_ERR_INVALID;
   m->have_rows = false;
   m->sparse = false;
   m->rows = rows;
@@ -154,6 +173,7 @@ extern "C" int gw_sdne_set_rows_csr(gw_sdne* m, const int64_t* offsets, const in
   if (!m) return gw_sdne_fail(nullptr, GW_ERR_INVALID, "NULL handle");
   if (!offsets || n < 1 || offsets[0] != 0) return gw_sdne_fail(m, GW_ERR_INVALID, "bad row arguments");
   if (n < m->B) return gw_sdne_fail(m, GW_ERR_INVALID, "%lld rows, fewer than the batch of %d", (long long)n, m->B);
+  if (!square_ok(m, n)) return GW_ERR_INVALID;
   for (int64_t r = 0; r < n; ++r)
     if (offsets[r + 1] < offsets[r]) return gw_sdne_fail(m, GW_ERR_INVALID, "offsets decrease at row %lld", (long long)r);
   const int64_t nnz = offsets[n];
@@ -292,19 +312,24 @@ static void product_dot(int64_t M, int64_t I, int64_t K, const float* a, const f
     }
 }
 
-// rows [row0, row0 + M) of the input as a dense [M][u0]
-static void host_stage(const gw_sdne* m, int64_t row0, int64_t M, std::vector<float>* x) {
+// rows ids[0..M) (NULL: row0, row0 + 1, ..) of the input as a dense [M][u0]
+static void host_stage(const gw_sdne* m, const int64_t* ids, int64_t row0, int64_t M, std::vector<float>* x) {
   const int64_t u0 = m->u[0];
   x->assign((size_t)(M * u0), 0.0f);
   for (int64_t b = 0; b < M; ++b) {
     float* xr = x->data() + b * u0;
+    const int64_t r = ids ? ids[b] : row0 + b;
     if (m->sparse) {
-      for (int64_t e = m->offs[(size_t)(row0 + b)]; e < m->offs[(size_t)(row0 + b + 1)]; ++e)
+      for (int64_t e = m->offs[(size_t)r]; e < m->offs[(size_t)(r + 1)]; ++e)
         xr[m->cols[(size_t)e]] = m->vals[(size_t)e];
     } else {
-      memcpy(xr, m->rows + (row0 + b) * m->pitch, (size_t)u0 * sizeof(float));
+      memcpy(xr, m->rows + r * m->pitch, (size_t)u0 * sizeof(float));
     }
   }
+}
+
+static void host_batch_rows(const gw_sdne* m, uint64_t t, int64_t* ids) {
+  for (int64_t i = 0; i < m->B; ++i) ids[i] = gw_sdne_row(m->p.seed, m->p.shuffle, m->N, m->B, t, i);
 }
 
 static void relu_of(const std::vector<float>& z, std::vector<float>* h) {
@@ -338,18 +363,44 @@ static void host_forward(const gw_sdne* m, int64_t M, bool full, HostAct* A) {
 static double host_gradient(const gw_sdne* m, uint64_t t, std::vector<float> g[8], bool want_loss) {
   const int* u = m->u;
   const int64_t B = m->B;
-  const int64_t nb = m->N / B;
-  const int64_t row0 = (int64_t)(t % (uint64_t)nb) * B;
   const float wd = (float)m->p.weight_decay;
+  const float bf = (float)m->p.nonzero_weight;
+  const float bw = bf * bf;
+  const double alpha = m->p.first_order;
+  std::vector<int64_t> ids((size_t)B);
+  host_batch_rows(m, t, ids.data());
   HostAct A;
-  host_stage(m, row0, B, &A.x);
+  host_stage(m, ids.data(), 0, B, &A.x);
   host_forward(m, B, true, &A);
   const float Bf = (float)B;
-  std::vector<float> dz4((size_t)(B * u[4])), dz3((size_t)(B * u[3])), dz2((size_t)(B * u[2])), dz1((size_t)(B * u[1]));
-  for (size_t i = 0; i < dz4.size(); ++i) {
-    const float d = A.y[i] - A.x[i];
-    dz4[i] = d / Bf;
+  // the first-order term: S[i][j] = a_ij + a_ji, g1 = coef * (the chain over j ascending)
+  std::vector<float> S, g1;
+  if (alpha > 0.0) {
+    const int64_t u0 = u[0], u2 = u[2];
+    S.resize((size_t)(B * B));
+    g1.resize((size_t)(B * u2));
+    for (int64_t i = 0; i < B; ++i)
+      for (int64_t j = 0; j < B; ++j)
+        S[(size_t)(i * B + j)] = A.x[(size_t)(i * u0 + ids[(size_t)j])] + A.x[(size_t)(j * u0 + ids[(size_t)i])];
+    const float coef = (float)(2.0 * alpha / (double)B);
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < B; ++i) {
+      const float* zi = A.z2.data() + i * u2;
+      float* gi = g1.data() + i * u2;
+      for (int64_t c = 0; c < u2; ++c) gi[c] = 0.0f;
+      for (int64_t j = 0; j < B; ++j) {
+        const float s = S[(size_t)(i * B + j)];
+        const float* zj = A.z2.data() + j * u2;
+        for (int64_t c = 0; c < u2; ++c) {
+          const float d = zi[c] - zj[c];
+          gi[c] = fmaf(s, d, gi[c]);
+        }
+      }
+      for (int64_t c = 0; c < u2; ++c) gi[c] = coef * gi[c];
+    }
   }
+  std::vector<float> dz4((size_t)(B * u[4])), dz3((size_t)(B * u[3])), dz2((size_t)(B * u[2])), dz1((size_t)(B * u[1]));
+  for (size_t i = 0; i < dz4.size(); ++i) dz4[i] = gw_sdne_dz4(A.y[i], A.x[i], bw, Bf);
   float qs = 0.0f;
   for (int64_t b = 0; b < B; ++b) {
     float rs = 0.0f;
@@ -366,6 +417,8 @@ static double host_gradient(const gw_sdne* m, uint64_t t, std::vector<float> g[8
     const float v = dz2[i] + klg;
     dz2[i] = A.z2[i] > 0.0f ? v : 0.0f;
   }
+  if (alpha > 0.0)
+    for (size_t i = 0; i < dz2.size(); ++i) dz2[i] = dz2[i] + g1[i];
   product_dot(B, u[1], u[2], dz2.data(), m->par[2].data(), dz1.data());
   for (size_t i = 0; i < dz1.size(); ++i) dz1[i] = A.z1[i] > 0.0f ? dz1[i] : 0.0f;
   const float* in[4] = {A.x.data(), A.h1.data(), A.h2.data(), A.h3.data()};
@@ -391,8 +444,21 @@ static double host_gradient(const gw_sdne* m, uint64_t t, std::vector<float> g[8
   double rec = 0.0;
   for (size_t i = 0; i < A.y.size(); ++i) {
     const double d = (double)A.y[i] - (double)A.x[i];
-    rec += d * d;
+    rec += (A.x[i] != 0.0f ? (double)bw : 1.0) * (d * d);
   }
+  double l1 = 0.0;
+  if (alpha > 0.0)
+    for (int64_t i = 0; i < B; ++i)
+      for (int64_t j = 0; j < B; ++j) {
+        const double a = (double)A.x[(size_t)(i * u[0] + ids[(size_t)j])];
+        if (a == 0.0) continue;
+        double s = 0.0;
+        for (int64_t c = 0; c < u[2]; ++c) {
+          const double d = (double)A.z2[(size_t)(i * u[2] + c)] - (double)A.z2[(size_t)(j * u[2] + c)];
+          s += d * d;
+        }
+        l1 += a * s;
+      }
   double reg = 0.0;
   for (int t8 = 0; t8 < 8; ++t8) {
     double s = 0.0;
@@ -401,7 +467,7 @@ static double host_gradient(const gw_sdne* m, uint64_t t, std::vector<float> g[8
   }
   const double p = m->p.kl_target, qd = (double)q;
   const double kl = p * log(p / (qd + 1e-8)) + (1.0 - p) * log((1.0 - p) / (1.0 - qd + 1e-8));
-  return rec / 2.0 / (double)B + m->p.weight_decay * reg / 2.0 + m->p.kl_weight * kl;
+  return rec / 2.0 / (double)B + m->p.weight_decay * reg / 2.0 + m->p.kl_weight * kl + alpha / (double)B * l1;
 }
 
 static int host_train(gw_sdne* m, int64_t step_begin, int64_t step_count, double* loss_out) {
@@ -444,6 +510,15 @@ extern "C" int gw_sdne_gradients(gw_sdne* m, int64_t step, float* const grads[8]
   return GW_OK;
 }
 
+extern "C" int gw_sdne_batch_rows(gw_sdne* m, int64_t step, int64_t* rows) {
+  const int rc = ready(m, step, 0);
+  if (rc != GW_OK) return rc;
+  if (!rows) return gw_sdne_fail(m, GW_ERR_INVALID, "NULL rows");
+  if (m->device >= 0) return gw_sdne_dev_batch_rows(m, step, rows);
+  host_batch_rows(m, (uint64_t)step, rows);
+  return GW_OK;
+}
+
 extern "C" int gw_sdne_encode(gw_sdne* m, int64_t row_begin, int64_t row_count, float* out) {
   const int rc = ready(m, 0, 0);
   if (rc != GW_OK) return rc;
@@ -456,7 +531,7 @@ extern "C" int gw_sdne_encode(gw_sdne* m, int64_t row_begin, int64_t row_count, 
   HostAct A;
   for (int64_t r0 = row_begin; r0 < row_begin + row_count; r0 += 256) {
     const int64_t M = std::min<int64_t>(256, row_begin + row_count - r0);
-    host_stage(m, r0, M, &A.x);
+    host_stage(m, nullptr, r0, M, &A.x);
     host_forward(m, M, false, &A);
     memcpy(m->enc.data() + r0 * u2, A.z2.data(), (size_t)(M * u2) * sizeof(float));
   }

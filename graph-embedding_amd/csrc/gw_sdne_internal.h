@@ -41,6 +41,7 @@ void gw_sdne_dev_free(gw_sdne* m);
 int gw_sdne_dev_set_rows(gw_sdne* m);  // after the handle's row fields are set: upload the CSR, size the encoding
 int gw_sdne_dev_train(gw_sdne* m, int64_t step_begin, int64_t step_count, double* loss_out, void* stream);
 int gw_sdne_dev_gradients(gw_sdne* m, int64_t step, float* const grads[8]);
+int gw_sdne_dev_batch_rows(gw_sdne* m, int64_t step, int64_t* rows);  // stages step's batch, copies its row ids back
 int gw_sdne_dev_encode(gw_sdne* m, int64_t row_begin, int64_t row_count, float* out);
 int gw_sdne_dev_export(gw_sdne* m, float* const par[8], float* const am[8], float* const av[8]);
 float* gw_sdne_dev_vectors(gw_sdne* m);  // the encoding in device memory, [N][u2]

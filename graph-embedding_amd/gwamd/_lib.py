@@ -125,19 +125,21 @@ class DeepSimParams(ctypes.Structure):
 class SdneParams(ctypes.Structure):
     """gw_sdne_params_t (include/graphwalk.h); struct_size is filled in by default; units = (u0, u1, u2, u3[, u4])."""
     _fields_ = [("struct_size", ctypes.c_int32), ("units", ctypes.c_int32 * 5), ("batch", ctypes.c_int32),
-                ("reserved0", ctypes.c_int32), ("learning_rate", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("shuffle", ctypes.c_int32), ("learning_rate", ctypes.c_double), ("beta1", ctypes.c_double),
                 ("beta2", ctypes.c_double), ("epsilon", ctypes.c_double), ("weight_decay", ctypes.c_double),
-                ("kl_weight", ctypes.c_double), ("kl_target", ctypes.c_double), ("seed", ctypes.c_uint64)]
+                ("kl_weight", ctypes.c_double), ("kl_target", ctypes.c_double), ("seed", ctypes.c_uint64),
+                ("nonzero_weight", ctypes.c_double), ("first_order", ctypes.c_double)]
 
     def __init__(self, units=(0, 400, 100, 300), batch=100, learning_rate=0.01, beta1=0.9, beta2=0.999, epsilon=1e-8,
-                 weight_decay=0.1, kl_weight=0.1, kl_target=0.005, seed=0):
+                 weight_decay=0.1, kl_weight=0.1, kl_target=0.005, seed=0, nonzero_weight=1.0, first_order=0.0,
+                 shuffle=0):
         u = [int(x) for x in units]
         if len(u) == 4:
             u.append(u[0])
         if len(u) != 5:
             raise ValueError("units must be (u0, u1, u2, u3) or (u0, u1, u2, u3, u4)")
-        super().__init__(ctypes.sizeof(SdneParams), (ctypes.c_int32 * 5)(*u), batch, 0, learning_rate, beta1, beta2,
-                         epsilon, weight_decay, kl_weight, kl_target, seed)
+        super().__init__(ctypes.sizeof(SdneParams), (ctypes.c_int32 * 5)(*u), batch, int(shuffle), learning_rate,
+                         beta1, beta2, epsilon, weight_decay, kl_weight, kl_target, seed, nonzero_weight, first_order)
 
 
 OVR_CONST_NEG = 0
@@ -299,6 +301,7 @@ SIGNATURES = {
     "gw_sdne_set_rows_csr": (ctypes.c_int, [P, P, P, P, I64]),
     "gw_sdne_train": (ctypes.c_int, [P, I64, I64, P, P]),
     "gw_sdne_gradients": (ctypes.c_int, [P, I64, PP]),
+    "gw_sdne_batch_rows": (ctypes.c_int, [P, I64, P]),
     "gw_sdne_encode": (ctypes.c_int, [P, I64, I64, P]),
     "gw_sdne_export": (ctypes.c_int, [P, PP, PP, PP]),
     "gw_sdne_vectors_dev": (ctypes.c_int, [P, PP, PI64]),

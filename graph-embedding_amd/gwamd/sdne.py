@@ -3,9 +3,13 @@
 The reference trains a four-layer dense autoencoder (TensorFlow 1, Adam, 200,000 steps of 100 rows taken in
 order) and returns the second layer's pre-activation of every row as its embedding.  Here the same model trains
 in HIP (gw_sdne_* in include/graphwalk.h) on a dense matrix or on sparse rows (a graph's adjacency, top-k SimRank
-rows); device=-1 evaluates the same law on the host, bit for bit.
+rows); device=-1 evaluates the same law on the host, bit for bit.  Three options, off by default, turn the
+reference's loss into the SDNE paper's loss for graphs: nonzero_weight (beta: an entry with x != 0 weighs beta^2 in
+the reconstruction term), first_order (alpha: (alpha / B) * sum a_ij |z2_i - z2_j|^2 over the rows of a batch; the
+rows must be a square matrix) and shuffle (a row permutation per epoch instead of batches of consecutive rows).
 
     python -m gwamd.sdne --input edges.txt --output graph.emb [--units 400,100,300] [--steps 200000]
+                         [--beta 5] [--alpha 0.1] [--shuffle]
     python -m gwamd.sdne --simrank x.sim.txt --output x.emb
     python -m gwamd.sdne --rows X.npy --output x.emb
 """
@@ -30,7 +34,9 @@ def _ptr8(arrs):
 
 
 class SdneModel:
-    """Owning handle over a gw_sdne trainer.  units = (u0, u1, u2, u3): the row width and the three hidden widths."""
+    """Owning handle over a gw_sdne trainer.  units = (u0, u1, u2, u3): the row width and the three hidden widths;
+    params: batch, learning_rate, beta1, beta2, epsilon, weight_decay, kl_weight, kl_target, seed, nonzero_weight
+    (beta), first_order (alpha), shuffle."""
 
     def __init__(self, units, device=0, **params):
         self.params = C.SdneParams(units=units, **params)
@@ -102,6 +108,12 @@ class SdneModel:
         C.check(C.lib().gw_sdne_gradients(self._h, step, _ptr8(g)), sdne=self._h)
         return dict(zip(TENSORS, g))
 
+    def batch_rows(self, step):
+        """The input rows step trains on, in slot order (int64 [batch])."""
+        out = np.empty(self.params.batch, np.int64)
+        C.check(C.lib().gw_sdne_batch_rows(self._h, step, C.ptr(out)), sdne=self._h)
+        return out
+
     def encode(self, row_begin=0, row_count=None):
         """z2 of the current rows [row_begin, +row_count) as float32 [row_count][u2]."""
         if row_count is None:
@@ -161,7 +173,8 @@ class SdneModel:
 
 def SDNE(Xtrain, XCV, Xtest, units=(400, 100, 300), steps=200000, device=0, **params):
     """SDNE.py:66-176: train on Xtrain only, return the encodings (Xtrain_, XCV_, Xtest_) as float32 arrays.
-    units: the three hidden widths; params: batch, learning_rate, weight_decay, kl_weight, kl_target, seed."""
+    units: the three hidden widths; params: batch, learning_rate, weight_decay, kl_weight, kl_target, seed, and
+    nonzero_weight, first_order (Xtrain square), shuffle.  XCV and Xtest are only encoded."""
     Xtrain = np.ascontiguousarray(Xtrain, np.float32)
     m = SdneModel((Xtrain.shape[1],) + tuple(units), device=device, **params)
     try:
@@ -173,9 +186,16 @@ def SDNE(Xtrain, XCV, Xtest, units=(400, 100, 300), steps=200000, device=0, **pa
             if len(X) == 0:
                 out.append(np.empty((0, m.dim), np.float32))
                 continue
-            pad = max(0, m.params.batch - len(X))  # a matrix shorter than the batch is padded, the padding dropped
-            m.set_rows(np.concatenate([X, np.zeros((pad, X.shape[1]), np.float32)]) if pad else X)
-            out.append(m.encode(0, len(X)))
+            # a matrix shorter than the batch is padded, the padding dropped; with first_order > 0 the handle takes
+            # square matrices only, so the rows go through in pieces of u0 rows, each padded to u0
+            piece = X.shape[1] if m.params.first_order > 0 else len(X)
+            enc = []
+            for r0 in range(0, len(X), piece):
+                Xp = X[r0:r0 + piece]
+                pad = max(0, (piece if m.params.first_order > 0 else m.params.batch) - len(Xp))
+                m.set_rows(np.concatenate([Xp, np.zeros((pad, X.shape[1]), np.float32)]) if pad else Xp)
+                enc.append(m.encode(0, len(Xp)))
+            out.append(np.concatenate(enc))
     finally:
         m.free()
     return tuple(out)
@@ -230,6 +250,11 @@ def cli(argv=None):
     ap.add_argument("--batch", type=int, default=100)
     ap.add_argument("--steps", type=int, default=200000)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--beta", type=float, default=1.0, help="weight of the nonzero entries in the reconstruction "
+                                                            "term (squared); the SDNE paper uses values above 1")
+    ap.add_argument("--alpha", type=float, default=0.0, help="weight of the first-order proximity term; needs square "
+                                                             "rows (--input always is)")
+    ap.add_argument("--shuffle", action="store_true", help="a row permutation per epoch instead of ordered batches")
     ap.add_argument("--groups", default=None, help="lines `node,label`: print classify.scoring's table")
     ap.add_argument("--neighbors", default=None, help="write the top-20 cosine neighbours there")
     ap.add_argument("--device", type=int, default=0)
@@ -238,25 +263,26 @@ def cli(argv=None):
     if len(hidden) != 3:
         raise SystemExit("--units takes three widths")
     labels = None
+    opts = dict(device=args.device, batch=args.batch, seed=args.seed, nonzero_weight=args.beta,
+                first_order=args.alpha, shuffle=int(args.shuffle))
     if args.input:
         from .graph import GWGraph
         weighted = args.weighted or _has_weights(args.input, args.delimiter)
         csr = GWGraph.from_edgelist(args.input, args.delimiter, "nx", False, weighted).export_csr()
         labels = [int(l) for l in csr["labels"]]
         n = len(csr["offsets"]) - 1
-        m = SdneModel((n,) + hidden, device=args.device, batch=args.batch, seed=args.seed)
+        m = SdneModel((n,) + hidden, **opts)
         m.set_csr(csr["offsets"], csr["nbrs"], csr["weights"] if weighted else None)
     elif args.simrank:
         from . import io
         offs, cols, vals = csr_from_simrank(io.read_simrank(args.simrank))
         n = len(offs) - 1
-        m = SdneModel((max(n, int(cols.max()) + 1 if len(cols) else 1),) + hidden, device=args.device,
-                       batch=args.batch, seed=args.seed)
+        m = SdneModel((max(n, int(cols.max()) + 1 if len(cols) else 1),) + hidden, **opts)
         m.set_csr(offs, cols, vals)
     else:
         X = np.load(args.rows)
         n = len(X)
-        m = SdneModel((X.shape[1],) + hidden, device=args.device, batch=args.batch, seed=args.seed)
+        m = SdneModel((X.shape[1],) + hidden, **opts)
         m.set_rows(X)
     m.train(0, args.steps, loss=False)
     emb = m.encode()

@@ -2,7 +2,8 @@
 // -DGW_SDNE_HOST_ONLY): sparse rows with an empty row and a row tail that is
 // never trained on, a reduction longer than one chunk, gradients, 3 training
 // steps in two pieces, the encoding, the state, then the same rows dense and
-// the error paths.  Meant to be built with -fsanitize=address,undefined and
+// the error paths, then the graph loss (nonzero_weight, first_order, shuffle)
+// on a square CSR matrix.  Meant to be built with -fsanitize=address,undefined and
 // run as a plain program; exit status 0 and "sdne host check ok" = clean.
 #include <math.h>
 #include <stdio.h>
@@ -38,6 +39,7 @@ int main() {
   p.kl_weight = 0.1;
   p.kl_target = 0.005;
   p.seed = 42;
+  p.nonzero_weight = 1.0;
   CHECK(gw_sdne_create(-1, &p, &m));
   uint32_t x = 12345u;
   auto next = [&x]() { return x = x * 1664525u + 1013904223u; };
@@ -107,6 +109,61 @@ int main() {
   gw_sdne* bad = nullptr;
   p.units[4] = u0 + 1;
   if (gw_sdne_create(-1, &p, &bad) != GW_ERR_INVALID || bad) return 1;
+  // the graph loss: weighted nonzeros, the first-order term and shuffled batches on a square CSR matrix with an
+  // empty row, a few steps across an epoch boundary and one gradients call
+  {
+    const int n = 2 * B + 3;
+    gw_sdne_params_t q = p;
+    q.units[0] = q.units[4] = n;
+    q.nonzero_weight = 3.0;
+    q.first_order = 0.7;
+    q.shuffle = 1;
+    CHECK(gw_sdne_create(-1, &q, &m));
+    std::vector<int64_t> so(n + 1, 0);
+    std::vector<int32_t> sc;
+    std::vector<float> sv;
+    for (int r = 0; r < n; ++r) {
+      for (int c = 0; c < n && r != 4; ++c)
+        if (c != r && (next() >> 8) % 3 == 0) {
+          sc.push_back(c);
+          sv.push_back(0.5f + 0.25f * (float)((next() >> 8) % 4));
+        }
+      so[(size_t)r + 1] = (int64_t)sc.size();
+    }
+    if (gw_sdne_set_rows_csr(m, so.data(), sc.data(), sv.data(), n - 1) != GW_ERR_INVALID) return 1;  // not square
+    CHECK(gw_sdne_set_rows_csr(m, so.data(), sc.data(), sv.data(), n));
+    std::vector<int64_t> ids((size_t)B);
+    std::vector<char> seen((size_t)n, 0);
+    for (int t = 0; t < 2; ++t) {  // epoch 0: 2B distinct rows
+      CHECK(gw_sdne_batch_rows(m, t, ids.data()));
+      for (const int64_t r : ids) {
+        if (r < 0 || r >= n || seen[(size_t)r]) return 1;
+        seen[(size_t)r] = 1;
+      }
+    }
+    double gl[5];
+    CHECK(gw_sdne_train(m, 0, 3, gl, nullptr));
+    CHECK(gw_sdne_train(m, 3, 2, gl + 3, nullptr));
+    const size_t gn[8] = {(size_t)n * u1, (size_t)u1, (size_t)u1 * u2, (size_t)u2,
+                          (size_t)u2 * u3, (size_t)u3, (size_t)u3 * n, (size_t)n};
+    std::vector<float> gg[8];
+    float* ggp[8];
+    for (int t = 0; t < 8; ++t) gg[t].resize(gn[t]), ggp[t] = gg[t].data();
+    CHECK(gw_sdne_gradients(m, 5, ggp));
+    std::vector<float> genc((size_t)n * u2);
+    CHECK(gw_sdne_encode(m, 0, n, genc.data()));
+    for (int i = 0; i < 5; ++i)
+      if (!isfinite(gl[i])) return 1;
+    for (const float v : gg[2])
+      if (!isfinite(v)) return 1;
+    gw_sdne_free(m);
+    q.nonzero_weight = 0.0;
+    if (gw_sdne_create(-1, &q, &bad) != GW_ERR_INVALID || bad) return 1;
+    q.nonzero_weight = 3.0, q.first_order = -1.0;
+    if (gw_sdne_create(-1, &q, &bad) != GW_ERR_INVALID || bad) return 1;
+    q.first_order = 0.7, q.shuffle = 2;
+    if (gw_sdne_create(-1, &q, &bad) != GW_ERR_INVALID || bad) return 1;
+  }
   printf("sdne host check ok: loss %.6f %.6f %.6f\n", loss[0], loss[1], loss[2]);
   return 0;
 }

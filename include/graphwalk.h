@@ -682,9 +682,17 @@ int gw_write_deepsim_text(const char* path, const float* w1, int64_t n, int dim)
  *          + kl_weight * KL(kl_target || mean(h2)),
  * TF1 Adam (lr_t as gw_deepsim) dense over all eight tensors.  Step t trains on
  * rows [(t mod nb) * batch, +batch), nb = floor(N / batch): the last N mod batch
- * rows are never trained on but are encoded.  The first-order proximity term
- * of the reference's docstring (not coded there) and the SDNE paper's weighting
- * of nonzero entries are not built.
+ * rows are never trained on but are encoded.  Three options, all off by default
+ * (the reference's law), make it the SDNE paper's loss for graphs:
+ *   nonzero_weight (beta): the reconstruction term weighs an entry with x != 0
+ *            by beta^2: sum(w * (y - x)^2) / 2 / batch;
+ *   first_order (alpha): adds (alpha / batch) * sum over rows i, j of the batch
+ *            of a_ij * |z2_i - z2_j|^2, a_ij = x_i[row(j)]: the rows must be a
+ *            square matrix (N = u0), else set_rows_* gives GW_ERR_INVALID;
+ *   shuffle: slot s = (t mod nb) * batch + i of epoch e = t / nb trains on row
+ *            perm_e(s), a keyed permutation of all N rows (tag "sdP0", iteration
+ *            e), so every row is trained on and edges fall inside batches;
+ *            gw_sdne_batch_rows names a step's rows.  Encodings stay in row order.
  * csrc/gw_sdne_law.h holds the one definition (float order, draws) that the
  * kernels and the host evaluation (device = -1) share; they agree bit for bit
  * (tested).  Every product reduces in chunks of 128 along its reduction index:
@@ -702,7 +710,7 @@ typedef struct gw_sdne_params_t {
   int32_t struct_size;  /* as gw_sgns_params_t.struct_size                        */
   int32_t units[5];     /* {u0 (required), 400, 100, 300, u4 (0 = u0)}            */
   int32_t batch;        /* 100                                                    */
-  int32_t reserved0;    /* 0                                                      */
+  int32_t shuffle;      /* 0 (ordered batches); 1: a row permutation per epoch    */
   double learning_rate; /* 0.01                                                   */
   double beta1;         /* 0.9                                                    */
   double beta2;         /* 0.999                                                  */
@@ -711,9 +719,14 @@ typedef struct gw_sdne_params_t {
   double kl_weight;     /* 0.1                                                    */
   double kl_target;     /* 0.005 (p)                                              */
   uint64_t seed;        /* 0                                                      */
+  double nonzero_weight; /* 1.0 (beta; finite, > 0)                               */
+  double first_order;   /* 0.0 (alpha; finite, >= 0)                              */
 } gw_sdne_params_t;
 /* device >= 0: a GPU; -1: the host evaluation.  Initialises w1..w4 (biases and
- * Adam state 0).  u4 != u0 gives GW_ERR_INVALID.                               */
+ * Adam state 0).  u4 != u0, a beta that is not finite and positive, an alpha
+ * that is not finite and non-negative, or a shuffle outside {0, 1} give
+ * GW_ERR_INVALID.  A struct_size that ends before a field leaves its default;
+ * a zeroed struct of the full size must set nonzero_weight itself.             */
 int gw_sdne_create(int device, const gw_sdne_params_t* params, gw_sdne** out);
 int gw_sdne_free(gw_sdne* m);
 const char* gw_sdne_last_error(const gw_sdne* m);
@@ -729,6 +742,9 @@ int gw_sdne_set_rows_csr(gw_sdne* m, const int64_t* offsets, const int32_t* cols
  * loss_out[step_count] (host, optional): each step's loss before its update.
  * Runs on `stream` and synchronises it.                                       */
 int gw_sdne_train(gw_sdne* m, int64_t step_begin, int64_t step_count, double* loss_out, void* stream);
+/* The rows step trains on, in slot order, into rows[batch] (host), for either
+ * setting of shuffle; a device handle stages the batch and reads the ids back. */
+int gw_sdne_batch_rows(gw_sdne* m, int64_t step, int64_t* rows);
 /* Gradient of step's batch at the current parameters (host copies, NULL
  * skips), weight decay included: grads = {w1[u0*u1], b1[u1], w2[u1*u2], b2,
  * w3[u2*u3], b3, w4[u3*u4], b4}.  Nothing is updated.                          */

@@ -8,6 +8,8 @@ Shapes: `ref`  units (784, 400, 100, 300, 784), B = 100, 1000 dense rows in devi
 Child processes, each under its own `timeout`:
   gw      ms per step of one gw_sdne_train call of --steps steps after a warm-up, the host clock around the
           synchronising call, the median of 5 calls;
+  graph   (blog only, its rows being a square matrix) the same gw measurement with the graph loss on
+          (nonzero_weight = 5, first_order = 0.1, shuffle), in the same run, beside the default law;
   torch   ms per step of the same model and Adam formula written in eager torch ops on the same GPU, fed batches
           built beforehand, the median of 5;
   --trace one gw run per shape under `rocprofv3 --kernel-trace --stats`: each kernel's share of a step, with the
@@ -31,14 +33,15 @@ sys.path.insert(0, os.path.join(ROOT, "graph-embedding_amd"))
 
 HIDDEN, B = (400, 100, 300), 100
 SHAPES = {"ref": 784, "blog": 10313}
+GRAPH = dict(nonzero_weight=5.0, first_order=0.1, shuffle=1)
 
 
-def make_trainer(shape):
+def make_trainer(shape, graph=False):
     import numpy as np
     from gwamd.sdne import SdneModel
     u0 = SHAPES[shape]
     rng = np.random.RandomState(0)
-    m = SdneModel((u0,) + HIDDEN, device=0, batch=B, seed=1)
+    m = SdneModel((u0,) + HIDDEN, device=0, batch=B, seed=1, **(GRAPH if graph else {}))
     if shape == "ref":
         X = (rng.uniform(0.2, 1.0, (1000, u0)) * (rng.uniform(size=(1000, u0)) < 0.19)).astype(np.float32)
         m.set_rows(X)
@@ -65,8 +68,8 @@ def median(xs):
     return xs[len(xs) // 2]
 
 
-def child_gw(shape, steps, warmup):
-    m, _ = make_trainer(shape)
+def child_gw(shape, steps, warmup, graph=False):
+    m, _ = make_trainer(shape, graph)
     m.train(0, warmup, loss=False)
     times, pos = [], warmup
     for _ in range(5):
@@ -142,10 +145,10 @@ def child_torch(shape, steps, warmup):
                       "ms_per_step_all": [1e3 * t / steps for t in times], "torch": torch.__version__}))
 
 
-def run_child(kind, shape, steps, warmup, limit, prefix=()):
+def run_child(kind, shape, steps, warmup, limit, prefix=(), graph=False):
     cmd = ["timeout", "-k", "10", str(limit)] + list(prefix) + [
         sys.executable, os.path.abspath(__file__), "--child", kind, "--shape", shape, "--steps", str(steps), "--warmup",
-        str(warmup)]
+        str(warmup)] + (["--graph"] if graph else [])
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         return {"error": f"exit {r.returncode}", "stderr": r.stderr[-1500:]}
@@ -155,14 +158,14 @@ def run_child(kind, shape, steps, warmup, limit, prefix=()):
     return {"error": "no result line", "stdout": r.stdout[-1500:]}
 
 
-def kernel_shares(shape, steps, warmup, limit):
+def kernel_shares(shape, steps, warmup, limit, graph=False):
     if shutil.which("rocprofv3") is None:
         return {"not_measured": "rocprofv3 not found"}
     d = tempfile.mkdtemp(prefix="sdne_kt_")
     try:
         res = run_child("gw", shape, steps, warmup, limit,
                         prefix=["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "kt",
-                                "--"])
+                                "--"], graph=graph)
         files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
         if "error" in res or not files:
             return {"not_measured": res.get("error", "no kernel trace written"), "stderr": res.get("stderr", "")}
@@ -193,9 +196,13 @@ def main():
     ap.add_argument("--trace", action="store_true", help="only the per-kernel shares (rocprofv3 --kernel-trace --stats)")
     ap.add_argument("--child", choices=["gw", "torch"])
     ap.add_argument("--shape", choices=sorted(SHAPES), default="ref")
+    ap.add_argument("--graph", action="store_true", help="child: the graph loss on")
     a = ap.parse_args()
     if a.child:
-        (child_gw if a.child == "gw" else child_torch)(a.shape, a.steps, a.warmup)
+        if a.child == "gw":
+            child_gw(a.shape, a.steps, a.warmup, a.graph)
+        else:
+            child_torch(a.shape, a.steps, a.warmup)
         return 0
     out = a.out or os.path.join(ROOT, "profiles", "sdne", "kernels.json" if a.trace else "bench.json")
     res, rc = {}, 0
@@ -207,11 +214,24 @@ def main():
             if "not_measured" in r["kernel_share_of_step"]:
                 rc = 1
                 break
+            if shape == "blog":
+                r["graph_kernel_share_of_step"] = kernel_shares(shape, min(a.steps, 40), 5, a.limit, graph=True)
+                if "not_measured" in r["graph_kernel_share_of_step"]:
+                    rc = 1
+                    break
             continue
         r["gw_sdne"] = run_child("gw", shape, a.steps, a.warmup, a.limit)
         if "error" in r["gw_sdne"]:   # nothing more is started on the GPU after a failed step
             rc = 1
             break
+        if shape == "blog":
+            r["graph_options"] = GRAPH
+            r["gw_sdne_graph"] = run_child("gw", shape, a.steps, a.warmup, a.limit, graph=True)
+            if "error" in r["gw_sdne_graph"]:
+                rc = 1
+                break
+            r["graph_minus_default_us_per_step"] = 1e3 * (r["gw_sdne_graph"]["ms_per_step"] -
+                                                          r["gw_sdne"]["ms_per_step"])
         r["torch_eager"] = run_child("torch", shape, a.steps, a.warmup, a.limit)
         if "error" in r["torch_eager"]:
             rc = 1
