@@ -79,6 +79,7 @@ extern "C" int gw_le_create(int device, int64_t n, const gw_le_params_t* params,
     return gw_le_fail(nullptr, GW_ERR_INVALID, "tol must be positive and min_eigenvalue a number");
   if (p.symmetrize != GW_LE_SYM_MEAN && p.symmetrize != GW_LE_SYM_MAX)
     return gw_le_fail(nullptr, GW_ERR_INVALID, "symmetrize %d", p.symmetrize);
+  if (p.self_loops != 0 && p.self_loops != 1) return gw_le_fail(nullptr, GW_ERR_INVALID, "self_loops %d", p.self_loops);
   if (device < -1) return gw_le_fail(nullptr, GW_ERR_INVALID, "device %d", device);
   if (n < 1 || n >= (int64_t)1 << 31) return gw_le_fail(nullptr, GW_ERR_INVALID, "n %lld out of range", (long long)n);
   if (device >= 0 && p.block > GW_LE_MAX_BLOCK)
@@ -132,7 +133,7 @@ int build_a(gw_le* m, Count count, At at, std::vector<int64_t>& off, std::vector
       if (x.j == -1) break;  // padding ends the row
       if (x.j < 0 || x.j >= n)
         return gw_le_fail(m, GW_ERR_RANGE, "row %lld: id %d outside [-1, %lld)", (long long)i, (int)x.j, (long long)n);
-      if (x.j == i || !(x.a > 0.0)) continue;  // self entries, NaN and non-positive weights
+      if ((x.j == i && !m->p.self_loops) || !(x.a > 0.0)) continue;  // self entries (unless kept), NaN and non-positive weights
       row.push_back(x);
     }
     std::stable_sort(row.begin(), row.end(), [](const Ent& a, const Ent& b) { return a.j < b.j; });

@@ -11,7 +11,13 @@
 // selection and the stopping rule are host code shared by both modes.
 //
 //   a_ij      the caller's entries: -1 ends a row; j == i, NaN and <= 0 are dropped; of what
-//             remains a repeated j keeps the last value
+//             remains a repeated j keeps the last value.  With self_loops = 1 (LE.py's own matrix:
+//             its knn lists the point itself, so W[i][i] = exp(0) = 1 stands in W and in D) an entry
+//             j == i is kept as a_ii under the same rules: it is its own transpose (mean and max of
+//             a_ii with itself are a_ii), counts in d_i and becomes the diagonal entry S_ii.  With
+//             y = s o u, u'(I - S)u = sum over i < j of w_ij (y_i - y_j)^2 (the diagonal cancels) and
+//             u'(I + S)u = sum over i < j of w_ij (y_i + y_j)^2 + sum over i of 2 w_ii y_i^2, both
+//             >= 0: the spectrum of S stays within [-1, 1] and the filter's interval holds.
 //   w_ij      (a_ij + a_ji) / 2 (GW_LE_SYM_MEAN) or max(a_ij, a_ji) (GW_LE_SYM_MAX), absent = 0
 //   d_i       w_ij added over j ascending from +0; d_i == 0: the row is isolated (s_i = 0, no entries)
 //   s_i       1 / sqrt(d_i);  S_ij = (w_ij * s_i) * s_j, CSR with ascending columns

@@ -20,6 +20,10 @@ Host-side mirror of the reference interfaces over the libgraphwalk C ABI
 * `gwamd.eigenmaps` — IsoMap_LE/simRank.py learn_embeddings (Laplacian eigenmaps of SimRank top-k
                       rows, or of a graph's adjacency), sparse and symmetrised, in fp64;
                       `python -m gwamd.eigenmaps --simrank X.sim.txt --output X.emb`
+* `gwamd.pointgraph` — IsoMap_LE/LE.py knn and heat-kernel weights: the k Euclidean nearest
+                      neighbours of device-resident points, in gw_topsim's row layout;
+                      eigenmaps.eigenmaps_of_points / laplaEigen chain it into the solver
+                      (`python -m gwamd.eigenmaps --points X.npy --knn 10 --heat 15`)
 * `gwamd.topsim`    — DeepSim/TopSimAll structures.Graph, TopSim_singleSample,
                       TopSim_Enumerate, SingleRandomWalk, SimRank (naive),
                       Print.printByOrder/printByOrderAll,

@@ -177,6 +177,15 @@ class KnnParams(ctypes.Structure):
         super().__init__(ctypes.sizeof(KnnParams), dim, topk, metric)
 
 
+class NngParams(ctypes.Structure):
+    """gw_nng_params_t (include/graphwalk.h); struct_size is filled in by default."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("dim", ctypes.c_int32), ("topk", ctypes.c_int32),
+                ("include_self", ctypes.c_int32), ("heat_t", ctypes.c_double)]
+
+    def __init__(self, dim=3, topk=10, include_self=1, heat_t=0.0):
+        super().__init__(ctypes.sizeof(NngParams), dim, topk, int(include_self), heat_t)
+
+
 LE_SYM_MEAN = 0
 LE_SYM_MAX = 1
 LE_CONVERGED = 0
@@ -187,12 +196,13 @@ class LeParams(ctypes.Structure):
     """gw_le_params_t (include/graphwalk.h); struct_size is filled in by default; block 0 = dim + 32."""
     _fields_ = [("struct_size", ctypes.c_int32), ("dim", ctypes.c_int32), ("block", ctypes.c_int32),
                 ("cheb_degree", ctypes.c_int32), ("max_iters", ctypes.c_int32), ("symmetrize", ctypes.c_int32),
-                ("tol", ctypes.c_double), ("min_eigenvalue", ctypes.c_double), ("seed", ctypes.c_uint64)]
+                ("tol", ctypes.c_double), ("min_eigenvalue", ctypes.c_double), ("seed", ctypes.c_uint64),
+                ("self_loops", ctypes.c_int32)]
 
     def __init__(self, dim=128, block=0, cheb_degree=20, max_iters=100, symmetrize=LE_SYM_MEAN, tol=1e-8,
-                 min_eigenvalue=1e-5, seed=0):
+                 min_eigenvalue=1e-5, seed=0, self_loops=0):
         super().__init__(ctypes.sizeof(LeParams), dim, block, cheb_degree, max_iters, symmetrize, tol, min_eigenvalue,
-                         seed)
+                         seed, int(self_loops))
 
 
 class LeStats(ctypes.Structure):
@@ -327,6 +337,14 @@ SIGNATURES = {
     "gw_knn_tiles": (ctypes.c_int, [P, PI32, PI32, PI32, PI32]),
     "gw_knn_fma_rate": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, PD]),
     "gw_topk_label_agreement": (ctypes.c_int, [P, I64, ctypes.c_int, P, P, P, I64, P]),
+    "gw_nng_create": (ctypes.c_int, [ctypes.c_int, I64, ctypes.POINTER(NngParams), PP]),
+    "gw_nng_free": (ctypes.c_int, [P]),
+    "gw_nng_last_error": (CP, [P]),
+    "gw_nng_set_vectors": (ctypes.c_int, [P, P, I64]),
+    "gw_nng_set_rows": (ctypes.c_int, [P, I64]),
+    "gw_nng_query": (ctypes.c_int, [P, P, I64, P, P, P, P]),
+    "gw_nng_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
+    "gw_nng_tiles": (ctypes.c_int, [P, PI32, PI32, PI32, PI32]),
     "gw_le_create": (ctypes.c_int, [ctypes.c_int, I64, ctypes.POINTER(LeParams), PP]),
     "gw_le_free": (ctypes.c_int, [P]),
     "gw_le_last_error": (CP, [P]),
@@ -366,14 +384,16 @@ def lib():
     return _lib
 
 
-def check(rc, handle=None, sgns=None, deepsim=None, ovr=None, knn=None, le=None, sdne=None):
+def check(rc, handle=None, sgns=None, deepsim=None, ovr=None, knn=None, le=None, sdne=None, nng=None):
     """Raise for a failing status; `handle` a gw_graph, `sgns` a gw_sgns, `deepsim` a gw_deepsim or True for a
-    handle-less gw_deepsim call, `ovr`, `knn`, `le` and `sdne` likewise for gw_ovr, gw_knn, gw_le and gw_sdne (for
-    the message)."""
+    handle-less gw_deepsim call, `ovr`, `knn`, `le`, `sdne` and `nng` likewise for gw_ovr, gw_knn, gw_le, gw_sdne and
+    gw_nng (for the message)."""
     if rc == GW_OK:
         return
     L = lib()
-    if sdne is not None:
+    if nng is not None:
+        msg = L.gw_nng_last_error(None if nng is True else nng)
+    elif sdne is not None:
         msg = L.gw_sdne_last_error(None if sdne is True else sdne)
     elif le is not None:
         msg = L.gw_le_last_error(None if le is True else le)

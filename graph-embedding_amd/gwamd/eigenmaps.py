@@ -9,9 +9,14 @@ law on the host, bit for bit.  The rows gw_topsim and gw_knn_query write (ids
 int32, scores float64, -1 padded) are the input as they are, and the result is
 an embedding classify.scoring and neighbors.most_similar read in place.
 
-    python -m gwamd.eigenmaps --simrank x.sim.txt | --input edges.txt [--delimiter D] --output x.emb
-        --dimensions 128 [--topk 10] [--symmetrize mean|max] [--min-eigenvalue 1e-5] [--block B]
-        [--groups g.csv] [--neighbors x.nn] [--device N]
+Points rather than a graph (LE.py's own input) go through gwamd.pointgraph first: their k
+Euclidean nearest neighbours with heat-kernel weights, fused on the GPU (gw_nng_*), then this
+solver with self_loops = 1, which keeps LE.py's W[i][i] = 1 (eigenmaps_of_points, laplaEigen).
+
+    python -m gwamd.eigenmaps --simrank x.sim.txt | --input edges.txt [--delimiter D] |
+        --points X.npy --knn 10 --heat 15.0 [--no-self]
+        --output x.emb --dimensions 128 [--topk 10] [--symmetrize mean|max] [--min-eigenvalue 1e-5]
+        [--block B] [--groups g.csv] [--neighbors x.nn] [--device N]
 """
 import argparse
 import ctypes
@@ -196,6 +201,34 @@ def eigenmaps(rows_or_graph, dim=128, device=0, labels=None, **params):
     return EigenEmbedding(m, [str(i) for i in range(m.n)] if labels is None else list(labels), lam, vec, res)
 
 
+def eigenmaps_of_points(x, k, t, dim=2, device=0, include_self=True, labels=None, **params):
+    """The Laplacian eigenmap of a point cloud: pointgraph.knn_graph(x, k, t, include_self) -> eigenmaps().  `x` is
+    what knn_graph takes (a torch CUDA tensor is read in place and decides the device); k counts the point itself
+    when include_self.  self_loops follows include_self unless given; the other params are eigenmaps()'s.  Returns
+    an EigenEmbedding."""
+    from . import pointgraph
+    from .neighbors import _vectors_of
+    x, device = _vectors_of(x, device)
+    ids, w = pointgraph.knn_graph(x, k, t, include_self=include_self, device=device)
+    params.setdefault("self_loops", int(bool(include_self)))
+    return eigenmaps((ids, w), dim=dim, device=device, labels=labels, **params)
+
+
+def laplaEigen(dataMat, k, t, dim=2, device=0, **params):
+    """IsoMap_LE/LE.py:35-51 by name and argument order: (lamda float64 [dim], f float64 [n][dim]), column c of f the
+    eigenvector of D^-1 (D - W) for lamda[c], W[i][j] = exp(-|x_i - x_j|^2 / t) over the k nearest neighbours of i,
+    i itself among them.  Departures from the reference:
+      - only the `dim` smallest eigenvalues above min_eigenvalue (default 1e-5, LE.py:74) and their vectors are
+        returned, ascending, not all n in np.linalg.eig's order; the leading eigenvalue 0 is skipped;
+      - W is symmetrised ((W + W') / 2, or symmetrize='max'); the reference uses the k-NN matrix as it is, so the
+        two agree where that matrix is already symmetric;
+      - the points are read as float32; f's columns have unit 2-norm and their largest entry positive;
+      - a point at distance > sqrt(700 t) has weight +0 and is no edge."""
+    x = np.ascontiguousarray(np.asarray(dataMat), np.float32)
+    emb = eigenmaps_of_points(x, k, t, dim=dim, device=device, include_self=True, **params)
+    return emb.eigenvalues, emb.vectors64
+
+
 def read_rows(path, topk=None):
     """(ids, scores) of a `.sim.txt`: the project's `v,id:score,...` through io.read_simrank, or the reference's
     space-separated form (IsoMap_LE/simRank.py:76-93); line r is vertex r.  topk: keep the first topk of a row."""
@@ -213,10 +246,14 @@ def read_rows(path, topk=None):
 
 
 def cli(argv=None):
-    ap = argparse.ArgumentParser(description="Laplacian eigenmaps of SimRank top-k rows or of a graph on MI355X.")
+    ap = argparse.ArgumentParser(description="Laplacian eigenmaps of SimRank top-k rows, of a graph or of points on MI355X.")
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--simrank", default=None, help="a .sim.txt: W from its top-k rows")
     src.add_argument("--input", default=None, help="an edge list: W is the graph's own adjacency")
+    src.add_argument("--points", default=None, help="a .npy matrix [n][d]: W from the rows' --knn nearest neighbours")
+    ap.add_argument("--knn", type=int, default=10, help="--points: neighbours per point, itself included (LE.py: 10)")
+    ap.add_argument("--heat", type=float, default=15.0, help="--points: t of exp(-d2 / t) (LE.py: 15.0); 0: weight 1")
+    ap.add_argument("--no-self", action="store_true", help="--points: a point is not its own neighbour, no self-loops")
     ap.add_argument("--delimiter", default=None)
     ap.add_argument("--output", required=True, help="embeddings (classify.read_embedding reads them)")
     ap.add_argument("--dimensions", type=int, default=128)
@@ -232,6 +269,12 @@ def cli(argv=None):
               block=args.block)
     if args.simrank:
         emb = eigenmaps(read_rows(args.simrank, args.topk), **kw)
+    elif args.points:
+        pts = np.load(args.points, allow_pickle=False)
+        if pts.ndim != 2:
+            ap.error("--points must hold a matrix [n][d]")
+        kw.pop("dim")
+        emb = eigenmaps_of_points(pts, args.knn, args.heat, dim=args.dimensions, include_self=not args.no_self, **kw)
     else:
         from .graph import GWGraph
         emb = eigenmaps(GWGraph.from_edgelist(args.input, args.delimiter), **kw)

@@ -958,8 +958,9 @@ int gw_topk_label_agreement(const int32_t* ids, int64_t nrows, int topk, const i
  * S u = (1 - lambda) u, f = s o u, s_i = 1 / sqrt(d_i)).  csrc/gw_le_law.h holds
  * the one definition kernels and host evaluation (device = -1) share; every sum
  * has one order, so the two agree bit for bit (tested).  All arithmetic is fp64.
- *   input     an entry with id -1 ends its row; an id equal to the row and a
- *             score that is NaN or <= 0 are dropped; of the entries that remain
+ *   input     an entry with id -1 ends its row; an id equal to the row (unless
+ *             self_loops = 1, below) and a score that is NaN or <= 0 are
+ *             dropped; of the entries that remain
  *             a repeated id keeps the last value; an id outside [-1, n) gives
  *             GW_ERR_RANGE;
  *   W         w_ij = (a_ij + a_ji) / 2 (GW_LE_SYM_MEAN) or max(a_ij, a_ji)
@@ -987,6 +988,11 @@ typedef struct gw_le_params_t {
   double min_eigenvalue; /* leading eigenvalues <= this are skipped (1e-5,
                             LE.py:74; simRank.py:137 uses 1e-2)                */
   uint64_t seed;         /* of the Philox start block                          */
+  int32_t self_loops;    /* 0 (default): an id equal to its row is dropped;
+                            1: it is kept as w_ii, counts in d_i and becomes a
+                            diagonal entry of S (IsoMap_LE/LE.py's matrix, whose
+                            knn lists the point itself); a caller passing a
+                            struct_size that ends before this field gets 0     */
 } gw_le_params_t;
 typedef struct gw_le_stats_t {
   int32_t state;       /* GW_LE_CONVERGED / GW_LE_NOT_CONVERGED                */
@@ -1033,6 +1039,67 @@ int gw_le_kernel_attrs(gw_le* m, int cap, const char** names, int32_t* vgprs, in
  * combine), 1 gram + reduce, 2 rotate.  After gw_le_solve; the blocks are
  * overwritten, the exported results are not.  ms = mean per launch.           */
 int gw_le_time_kernel(gw_le* m, int which, int reps, double* ms);
+
+/* ---- neighbour graph of points ---------------------------------------------- */
+/* Replaces the first two steps of IsoMap_LE/LE.py:35-60 (laplaEigen's knn and its
+ * heat-kernel weights): for every source row of an fp32 matrix the topk rows at
+ * the smallest Euclidean distance and W = exp(-|x_i - x_j|^2 / t), in gw_topsim's
+ * row layout, so gw_le_set_rows (with self_loops = 1: LE.py's own matrix) and
+ * gw_write_sim_text_topk take them as they are.  csrc/gw_nng_law.h holds the one
+ * definition the kernels and the host evaluation (device = -1) share; they agree
+ * bit for bit (tested).
+ *   arithmetic  features are the caller's fp32 widened, everything else fp64;
+ *   d2(i,j)     e = x[i][k] - x[j][k], acc = fma(e, e, acc) over k = 0 .. dim-1
+ *               ascending from +0 (the reference's difference form): never
+ *               negative, exactly 0 for equal rows, d2(i,j) and d2(j,i) have the
+ *               same bits; no split-K, no reassociation;
+ *   row of v    the candidates j != v with d2(v,j) neither NaN nor +inf, by d2
+ *               ascending, then id ascending (a total order: nothing depends on
+ *               tiles, grid or timing).  include_self = 0: the first topk of
+ *               them.  include_self = 1 (LE.py's knn: a point is its own nearest
+ *               neighbour): entry 0 is (v, d2 0, weight 1.0), then the first
+ *               topk - 1 candidates.  Where other rows equal row v exactly,
+ *               numpy's argsort may list one of them first and leave v out of the
+ *               reference's row; here v always leads.  A row with fewer listed
+ *               entries is padded with (-1, 0.0), d2 0.0;
+ *   weight      heat_t > 0: exp(-(d2 / heat_t)) by the project's fp64 exp
+ *               (gw_ovr_law.h): exactly 1.0 at d2 = 0 and +0 once d2 / heat_t
+ *               exceeds 700 (listed, but no edge for gw_le); heat_t == 0: every
+ *               listed weight is 1.0.
+ * Device path: 1 <= dim <= 1024, 1 <= topk <= 128, n < 2^31 (else
+ * GW_ERR_UNSUPPORTED); the host path takes any size.                          */
+typedef struct gw_nng gw_nng;
+typedef struct gw_nng_params_t {
+  int32_t struct_size;  /* as gw_sgns_params_t.struct_size                     */
+  int32_t dim;          /* columns read of a row (3)                           */
+  int32_t topk;         /* entries per output row, the source included (10)    */
+  int32_t include_self; /* 1 (default): the source is entry 0 of its row; 0    */
+  double heat_t;        /* t of the heat kernel; 0 (default): unit weights;
+                           negative or NaN: GW_ERR_INVALID                     */
+} gw_nng_params_t;
+/* device >= 0: a GPU; -1: the host evaluation.  n = rows of the matrix         */
+int gw_nng_create(int device, int64_t n, const gw_nng_params_t* params, gw_nng** out);
+int gw_nng_free(gw_nng* m);
+const char* gw_nng_last_error(const gw_nng* m);
+/* As gw_knn_set_vectors / gw_knn_set_rows: the matrix is read where it lies
+ * (zero-copy from gw_sgns_vectors_dev, gw_le_vectors_dev, ...), only dim floats
+ * of a row are ever read, and it must outlive the queries.                    */
+int gw_nng_set_vectors(gw_nng* m, const float* x, int64_t pitch);
+int gw_nng_set_rows(gw_nng* m, int64_t n);
+/* out_ids[r * topk + t] (int32), out_weights[r * topk + t] (double) and, where
+ * out_d2 is not NULL, out_d2[r * topk + t] (double, the squared distance) of the
+ * source sources[r], r < nsrc.  Pointers, sources == NULL, repeated sources,
+ * nsrc == 0, GW_ERR_RANGE with nothing written, GW_ERR_STATE and the stream are
+ * as in gw_knn_query.                                                         */
+int gw_nng_query(gw_nng* m, const int32_t* sources, int64_t nsrc, int32_t* out_ids, double* out_weights,
+                 double* out_d2, void* stream);
+/* As gw_ovr_kernel_attrs: this family's kernels only                          */
+int gw_nng_kernel_attrs(gw_nng* m, int cap, const char** names, int32_t* vgprs, int32_t* scratch_bytes,
+                        int32_t* lds_bytes, int32_t* count);
+/* As gw_knn_tiles: tq source rows per workgroup, tc candidate rows per tile, kc
+ * columns per LDS chunk, buf = entries of a row's candidate buffer for this
+ * handle's topk.  GW_ERR_STATE for a host handle.                             */
+int gw_nng_tiles(const gw_nng* m, int32_t* tq, int32_t* tc, int32_t* kc, int32_t* buf);
 
 /* ---- multi-GPU exchange (RCCL over xGMI) ---------------------------------- */
 /* the graph is replicated and units (walks, TopSim sources) are
