@@ -29,7 +29,8 @@ CXX_SRCS = ["gw_graph_host.cpp", "gw_capi.cpp", "gw_comm.cpp", "gw_sgns_host.cpp
 HEADERS = ["gw_internal.h", "gw_philox.h", "gw_device_common.h", "gw_sgns_law.h", "gw_sgns_internal.h",
            "gw_deepsim_law.h", "gw_deepsim_internal.h", "gw_ovr_law.h", "gw_ovr_internal.h",
            "gw_knn_law.h", "gw_knn_internal.h", "gw_le_law.h", "gw_le_internal.h", "gw_sdne_law.h",
-           "gw_sdne_internal.h", "gw_nng_law.h", "gw_nng_internal.h", "gw_trainer_fail.h", "gw_trainer_device.h"]
+           "gw_sdne_internal.h", "gw_nng_law.h", "gw_nng_internal.h", "gw_trainer_fail.h", "gw_trainer_device.h",
+           "gw_pairs_topk.h", "gw_pairs_host.h"]
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",

@@ -10,8 +10,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <algorithm>
-#include <new>
 #include <utility>
 #include <vector>
 
@@ -44,13 +42,6 @@ extern "C" int gw_knn_fma_rate(gw_knn* m, int, int, double*) { return no_dev(m);
 
 extern "C" const char* gw_knn_last_error(const gw_knn* m) { return m ? m->err.c_str() : g_knn_err.c_str(); }
 
-static int check_rows(gw_knn* m, int device, int64_t n) {
-  if (n < 1 || n >= (int64_t)1 << 40) return gw_knn_fail(m, GW_ERR_INVALID, "n %lld out of range", (long long)n);
-  if (device >= 0 && n >= (int64_t)1 << 31)
-    return gw_knn_fail(m, GW_ERR_UNSUPPORTED, "n %lld: the kernels take n < 2^31 (device = -1 takes any)", (long long)n);
-  return GW_OK;
-}
-
 extern "C" int gw_knn_create(int device, int64_t n, const gw_knn_params_t* params, gw_knn** out) {
   if (!out) return gw_knn_fail(nullptr, GW_ERR_INVALID, "NULL out");
   *out = nullptr;
@@ -59,36 +50,11 @@ extern "C" int gw_knn_create(int device, int64_t n, const gw_knn_params_t* param
   p.dim = 128;
   p.topk = 20;
   p.metric = GW_KNN_COSINE;
-  if (params) {
-    if (params->struct_size < (int32_t)sizeof(int32_t))
-      return gw_knn_fail(nullptr, GW_ERR_INVALID, "gw_knn_params_t.struct_size %d", (int)params->struct_size);
-    memcpy(&p, params, std::min((size_t)params->struct_size, sizeof p));
-  }
-  p.struct_size = (int32_t)sizeof p;
+  const int rc = gw_pairs_read_params<gw_knn>(params, &p, "gw_knn_params_t");
+  if (rc != GW_OK) return rc;
   if (p.dim < 1 || p.topk < 1) return gw_knn_fail(nullptr, GW_ERR_INVALID, "dim %d and topk %d must be positive", p.dim, p.topk);
   if (p.metric != GW_KNN_COSINE && p.metric != GW_KNN_DOT) return gw_knn_fail(nullptr, GW_ERR_INVALID, "metric %d", p.metric);
-  if (device < -1) return gw_knn_fail(nullptr, GW_ERR_INVALID, "device %d", device);
-  int rc = check_rows(nullptr, device, n);
-  if (rc != GW_OK) return rc;
-  if (device >= 0 && (p.dim > GW_KNN_MAX_DIM || p.topk > GW_KNN_MAX_TOPK))
-    return gw_knn_fail(nullptr, GW_ERR_UNSUPPORTED, "dim %d / topk %d: the kernels take dim <= %d and topk <= %d "
-                       "(device = -1 takes any)", p.dim, p.topk, GW_KNN_MAX_DIM, GW_KNN_MAX_TOPK);
-  gw_knn* m = new (std::nothrow) gw_knn();
-  if (!m) return gw_knn_fail(nullptr, GW_ERR_NOMEM, "out of memory");
-  m->device = device;
-  m->p = p;
-  m->n = n;
-  if (device >= 0) {
-    rc = gw_knn_dev_alloc(m);
-    if (rc != GW_OK) {
-      g_knn_err = m->err;
-      gw_knn_dev_free(m);
-      delete m;
-      return rc;
-    }
-  }
-  *out = m;
-  return GW_OK;
+  return gw_pairs_create(device, n, p, GW_KNN_MAX_DIM, GW_KNN_MAX_TOPK, gw_knn_dev_alloc, gw_knn_dev_free, &g_knn_err, out);
 }
 
 extern "C" int gw_knn_free(gw_knn* m) {
@@ -98,60 +64,44 @@ extern "C" int gw_knn_free(gw_knn* m) {
   return GW_OK;
 }
 
-extern "C" int gw_knn_set_rows(gw_knn* m, int64_t n) {
-  if (!m) return gw_knn_fail(nullptr, GW_ERR_INVALID, "NULL handle");
-  const int rc = check_rows(m, m->device, n);
-  if (rc != GW_OK) return rc;
-  m->n = n;
-  m->have_x = false;  // the vectors set before had another row count
-  return GW_OK;
-}
+extern "C" int gw_knn_set_rows(gw_knn* m, int64_t n) { return gw_pairs_set_rows(m, n); }
 
-extern "C" int gw_knn_set_vectors(gw_knn* m, const float* x, int64_t pitch) {
-  if (!m) return gw_knn_fail(nullptr, GW_ERR_INVALID, "NULL handle");
-  if (!x || pitch < m->p.dim) return gw_knn_fail(m, GW_ERR_INVALID, "NULL vectors or pitch below dim");
-  m->x = x;
-  m->pitch = pitch;
-  m->have_x = true;
-  return GW_OK;
-}
+extern "C" int gw_knn_set_vectors(gw_knn* m, const float* x, int64_t pitch) { return gw_pairs_set_vectors(m, x, pitch); }
 
 // ---- the law on the host -------------------------------------------------------
-static void host_query(const gw_knn* m, const int32_t* sources, int64_t nsrc, int32_t* out_ids, double* out_scores) {
-  const int dim = m->p.dim, metric = m->p.metric;
-  const int64_t n = m->n, topk = m->p.topk;
-  std::vector<double> nrm;
-  if (metric == GW_KNN_COSINE) {
-    nrm.resize((size_t)n);
-#pragma omp parallel for schedule(static)
-    for (int64_t j = 0; j < n; ++j) nrm[(size_t)j] = gw_knn_nrm(m->x + j * m->pitch, dim);
+namespace {
+struct HostLaw {
+  const gw_knn* m;
+  const double* nrm;  // [n] under GW_KNN_COSINE
+  int64_t keep;
+  int32_t* out_ids;
+  double* out_scores;
+  bool score(int64_t v, int64_t j, double* s) const {
+    const int metric = m->p.metric;
+    const double nv = metric == GW_KNN_COSINE ? nrm[v] : 0.0, nj = metric == GW_KNN_COSINE ? nrm[j] : 0.0;
+    *s = gw_knn_score(metric, gw_knn_dot(m->x + v * m->pitch, m->x + j * m->pitch, m->p.dim), nv, nj);
+    return gw_knn_listed(metric, *s, nv, nj) != 0;
   }
-  const auto before = [](const std::pair<double, int32_t>& a, const std::pair<double, int32_t>& b) {
-    return gw_knn_before(a.first, a.second, b.first, b.second) != 0;
-  };
-#pragma omp parallel
-  {
-    std::vector<std::pair<double, int32_t>> cand;
-#pragma omp for schedule(dynamic, 8)
-    for (int64_t r = 0; r < nsrc; ++r) {
-      const int64_t v = sources ? sources[r] : r;
-      const float* xv = m->x + v * m->pitch;
-      const double nv = metric == GW_KNN_COSINE ? nrm[(size_t)v] : 0.0;
-      cand.clear();
-      for (int64_t j = 0; j < n; ++j) {
-        if (j == v) continue;
-        const double nj = metric == GW_KNN_COSINE ? nrm[(size_t)j] : 0.0;
-        const double s = gw_knn_score(metric, gw_knn_dot(xv, m->x + j * m->pitch, dim), nv, nj);
-        if (gw_knn_listed(metric, s, nv, nj)) cand.emplace_back(s, (int32_t)j);
-      }
-      const size_t keep = std::min<size_t>(cand.size(), (size_t)topk);
-      std::partial_sort(cand.begin(), cand.begin() + (ptrdiff_t)keep, cand.end(), before);
-      for (int64_t t = 0; t < topk; ++t) {
-        out_ids[r * topk + t] = (size_t)t < keep ? cand[(size_t)t].second : -1;
-        out_scores[r * topk + t] = (size_t)t < keep ? cand[(size_t)t].first : 0.0;
-      }
+  static int before(double sa, int32_t ia, double sb, int32_t ib) { return gw_knn_before(sa, ia, sb, ib); }
+  void write_row(int64_t r, int64_t, const std::pair<double, int32_t>* cand, size_t kept) const {
+    const int64_t topk = m->p.topk;
+    for (int64_t t = 0; t < topk; ++t) {
+      out_ids[r * topk + t] = (size_t)t < kept ? cand[t].second : -1;
+      out_scores[r * topk + t] = (size_t)t < kept ? cand[t].first : 0.0;
     }
   }
+};
+}  // namespace
+
+static void host_query(const gw_knn* m, const int32_t* sources, int64_t nsrc, int32_t* out_ids, double* out_scores) {
+  const int64_t n = m->n;
+  std::vector<double> nrm;
+  if (m->p.metric == GW_KNN_COSINE) {
+    nrm.resize((size_t)n);
+#pragma omp parallel for schedule(static)
+    for (int64_t j = 0; j < n; ++j) nrm[(size_t)j] = gw_knn_nrm(m->x + j * m->pitch, m->p.dim);
+  }
+  gw_pairs_host_rows(HostLaw{m, nrm.data(), m->p.topk, out_ids, out_scores}, n, sources, nsrc);
 }
 
 extern "C" int gw_knn_query(gw_knn* m, const int32_t* sources, int64_t nsrc, int32_t* out_ids, double* out_scores,
@@ -163,11 +113,8 @@ extern "C" int gw_knn_query(gw_knn* m, const int32_t* sources, int64_t nsrc, int
   if (nsrc == 0) return GW_OK;
   if (!out_ids || !out_scores) return gw_knn_fail(m, GW_ERR_INVALID, "NULL output");
   if (m->device >= 0) return gw_knn_dev_query(m, sources, nsrc, out_ids, out_scores, stream);
-  if (sources)
-    for (int64_t r = 0; r < nsrc; ++r)
-      if (sources[r] < 0 || sources[r] >= m->n)
-        return gw_knn_fail(m, GW_ERR_RANGE, "entry %lld: source %d outside [0, %lld)", (long long)r, (int)sources[r],
-                           (long long)m->n);
+  const int rc = gw_pairs_check_sources(m, sources, nsrc);
+  if (rc != GW_OK) return rc;
   host_query(m, sources, nsrc, out_ids, out_scores);
   return GW_OK;
 }

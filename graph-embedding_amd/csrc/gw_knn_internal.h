@@ -3,24 +3,16 @@
 #pragma once
 #include <stdint.h>
 
-#include <string>
-
-#include "../../include/graphwalk.h"
 #include "gw_knn_law.h"
+#include "gw_pairs_host.h"
 
-struct gw_knn {
-  int device = -1;  // -1: host evaluation
+struct gw_knn : gw_pairs_handle {
   gw_knn_params_t p{};
-  int64_t n = 0;
-  const float* x = nullptr;  // caller's rows (host or device memory)
-  int64_t pitch = 0;
-  bool have_x = false;
   struct gw_knn_dev* dev = nullptr;  // device state (device >= 0), defined and owned by gw_knn.hip
-  std::string err;
 };
 
 int gw_knn_fail(gw_knn* m, int code, const char* fmt, ...);
-inline auto gw_fail_of(const gw_knn*) { return &gw_knn_fail; }  // for the shared device plumbing
+inline auto gw_fail_of(const gw_knn*) { return &gw_knn_fail; }  // for the shared plumbing (gw_pairs_host.h, gw_pairs_topk.h)
 
 // device entry points (gw_knn.hip)
 int gw_knn_dev_alloc(gw_knn* m);

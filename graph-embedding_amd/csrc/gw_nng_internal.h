@@ -3,24 +3,16 @@
 #pragma once
 #include <stdint.h>
 
-#include <string>
-
-#include "../../include/graphwalk.h"
 #include "gw_nng_law.h"
+#include "gw_pairs_host.h"
 
-struct gw_nng {
-  int device = -1;  // -1: host evaluation
+struct gw_nng : gw_pairs_handle {
   gw_nng_params_t p{};
-  int64_t n = 0;
-  const float* x = nullptr;  // caller's rows (host or device memory)
-  int64_t pitch = 0;
-  bool have_x = false;
   struct gw_nng_dev* dev = nullptr;  // device state (device >= 0), defined and owned by gw_nng.hip
-  std::string err;
 };
 
 int gw_nng_fail(gw_nng* m, int code, const char* fmt, ...);
-inline auto gw_fail_of(const gw_nng*) { return &gw_nng_fail; }  // for the shared device plumbing
+inline auto gw_fail_of(const gw_nng*) { return &gw_nng_fail; }  // for the shared plumbing (gw_pairs_host.h, gw_pairs_topk.h)
 
 // device entry points (gw_nng.hip)
 int gw_nng_dev_alloc(gw_nng* m);

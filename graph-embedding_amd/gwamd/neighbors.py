@@ -29,14 +29,23 @@ except Exception:  # pragma: no cover - torch is optional for the host path
 METRICS = {"cosine": C.KNN_COSINE, "dot": C.KNN_DOT}
 
 
-class Neighbors:
-    """Owning handle over a gw_knn."""
+class _PairsHandle:
+    """What the owning handles over gw_knn and gw_nng share; `_prefix` is the C prefix and the C.check keyword."""
 
-    def __init__(self, n, device=0, dim=128, topk=20, metric="cosine"):
-        self.params = C.KnnParams(dim=int(dim), topk=int(topk), metric=METRICS.get(metric, metric))
+    _prefix = None
+
+    def _fn(self, name):
+        return getattr(C.lib(), f"gw_{self._prefix}_{name}")
+
+    def _call(self, name, *args):
+        C.check(self._fn(name)(self._h, *args), **{self._prefix: self._h})
+
+    def _create(self, n, device, params):
+        self.params = params
         self.n, self.device = int(n), int(device)
         h = ctypes.c_void_p()
-        C.check(C.lib().gw_knn_create(self.device, self.n, ctypes.byref(self.params), ctypes.byref(h)), knn=True)
+        C.check(self._fn("create")(self.device, self.n, ctypes.byref(self.params), ctypes.byref(h)),
+                **{self._prefix: True})
         self._h = h
         self._keep = []
 
@@ -46,7 +55,7 @@ class Neighbors:
 
     def set_rows(self, n):
         """Another row count for the next set_vectors."""
-        C.check(C.lib().gw_knn_set_rows(self._h, int(n)), knn=self._h)
+        self._call("set_rows", int(n))
         self.n = int(n)
         self._keep = []
 
@@ -68,7 +77,44 @@ class Neighbors:
             pitch = x.stride(0) if hasattr(x, "stride") else x.strides[0] // 4
             p = C.ptr(x)
             self._keep = [x]
-        C.check(C.lib().gw_knn_set_vectors(self._h, p, int(pitch)), knn=self._h)
+        self._call("set_vectors", p, int(pitch))
+
+    def tiles(self):
+        """{'tq', 'tc', 'kc', 'buf'}: the main kernel's launch geometry and the per-row buffer length."""
+        v = [ctypes.c_int32() for _ in range(4)]
+        self._call("tiles", *[ctypes.byref(t) for t in v])
+        return dict(zip(("tq", "tc", "kc", "buf"), (t.value for t in v)))
+
+    def kernel_attrs(self):
+        """{kernel name: {'vgprs', 'scratch_bytes', 'lds_bytes'}} (hipFuncGetAttributes)."""
+        cap = 16
+        names = (ctypes.c_char_p * cap)()
+        v, s, l = ((ctypes.c_int32 * cap)() for _ in range(3))
+        n = ctypes.c_int32()
+        self._call("kernel_attrs", cap, names, v, s, l, ctypes.byref(n))
+        return {names[i].decode(): {"vgprs": v[i], "scratch_bytes": s[i], "lds_bytes": l[i]}
+                for i in range(min(n.value, cap))}
+
+    def free(self):
+        if getattr(self, "_h", None):
+            self._fn("free")(self._h)
+            self._h = None
+            self._keep = []
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+class Neighbors(_PairsHandle):
+    """Owning handle over a gw_knn."""
+
+    _prefix = "knn"
+
+    def __init__(self, n, device=0, dim=128, topk=20, metric="cosine"):
+        self._create(n, device, C.KnnParams(dim=int(dim), topk=int(topk), metric=METRICS.get(metric, metric)))
 
     def query(self, sources=None, stream=None):
         """(ids int32 [nsrc][topk], scores float64 [nsrc][topk]) as numpy arrays; sources None: every row."""
@@ -79,7 +125,7 @@ class Neighbors:
         if self.device < 0:
             ids = np.empty((nsrc, topk), np.int32)
             sc = np.empty((nsrc, topk), np.float64)
-            C.check(C.lib().gw_knn_query(self._h, C.ptr(sources), nsrc, C.ptr(ids), C.ptr(sc), None), knn=self._h)
+            self._call("query", C.ptr(sources), nsrc, C.ptr(ids), C.ptr(sc), None)
             return ids, sc
         dev = f"cuda:{self.device}"
         src = None if sources is None else torch.as_tensor(sources, device=dev)
@@ -87,42 +133,14 @@ class Neighbors:
         sc = torch.empty((nsrc, topk), dtype=torch.float64, device=dev)
         if stream is None:
             stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        C.check(C.lib().gw_knn_query(self._h, C.ptr(src), nsrc, C.ptr(ids), C.ptr(sc), stream), knn=self._h)
+        self._call("query", C.ptr(src), nsrc, C.ptr(ids), C.ptr(sc), stream)
         return ids.cpu().numpy(), sc.cpu().numpy()
-
-    def tiles(self):
-        """{'tq', 'tc', 'kc', 'buf'}: the main kernel's launch geometry and the per-row buffer length."""
-        v = [ctypes.c_int32() for _ in range(4)]
-        C.check(C.lib().gw_knn_tiles(self._h, *[ctypes.byref(t) for t in v]), knn=self._h)
-        return dict(zip(("tq", "tc", "kc", "buf"), (t.value for t in v)))
 
     def fma_rate(self, blocks=2048, iters=20000):
         """fp64 fused multiply-adds per second of 16 independent chains per lane (the main loop's ceiling)."""
         r = ctypes.c_double()
-        C.check(C.lib().gw_knn_fma_rate(self._h, int(blocks), int(iters), ctypes.byref(r)), knn=self._h)
+        self._call("fma_rate", int(blocks), int(iters), ctypes.byref(r))
         return r.value
-
-    def kernel_attrs(self):
-        """{kernel name: {'vgprs', 'scratch_bytes', 'lds_bytes'}} (hipFuncGetAttributes)."""
-        cap = 16
-        names = (ctypes.c_char_p * cap)()
-        v, s, l = ((ctypes.c_int32 * cap)() for _ in range(3))
-        n = ctypes.c_int32()
-        C.check(C.lib().gw_knn_kernel_attrs(self._h, cap, names, v, s, l, ctypes.byref(n)), knn=self._h)
-        return {names[i].decode(): {"vgprs": v[i], "scratch_bytes": s[i], "lds_bytes": l[i]}
-                for i in range(min(n.value, cap))}
-
-    def free(self):
-        if getattr(self, "_h", None):
-            C.lib().gw_knn_free(self._h)
-            self._h = None
-            self._keep = []
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
 
 
 def _vectors_of(vectors, device):

@@ -230,6 +230,9 @@ def test_kernel_attrs():
     print("gw_knn_kernel_attrs (topk 20):", a)
     print("gw_knn_kernel_attrs (topk 128):", b)
     assert set(a) == {"k_knn_check", "k_knn_norms", "k_knn_main"}
+    for name, k in a.items():
+        assert k["scratch_bytes"] == 0, name
+        assert 0 < k["vgprs"] <= 128, name           # two workgroups of 256 lanes per CU keep their registers
 
 
 def sim_rows(path):

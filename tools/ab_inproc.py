@@ -28,7 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "graph-embedding_amd"))
 def load(path, C):
     L = ctypes.CDLL(path)
     for name, (res, args) in C.SIGNATURES.items():
-        f = getattr(L, name, None)  # older builds (tools/build_rev_lib.sh) lack newer entry points
+        f = getattr(L, name, None)  # a library built from an older revision (its own build.py) lacks newer entry points
         if f is None:
             continue
         f.restype = res
