@@ -78,6 +78,7 @@ const char* gw_strerror(int code) {
     case GW_ERR_KEY: return "missing key";
     case GW_ERR_ZERODIV: return "division by zero";
     case GW_ERR_CAPACITY: return "capacity exceeded";
+    case GW_ERR_INTERNAL: return "internal error";
     default: return "unknown error";
   }
 }

@@ -31,6 +31,7 @@ GW_ERR_RANGE = -8
 GW_ERR_KEY = -9
 GW_ERR_ZERODIV = -10
 GW_ERR_CAPACITY = -11
+GW_ERR_INTERNAL = -12
 
 SEM_NX_SIMPLE = 0
 SEM_JAVA_MULTI = 1
@@ -184,6 +185,25 @@ class NngParams(ctypes.Structure):
 
     def __init__(self, dim=3, topk=10, include_self=1, heat_t=0.0):
         super().__init__(ctypes.sizeof(NngParams), dim, topk, int(include_self), heat_t)
+
+
+GEO_SYM_UNION = 0
+GEO_DIRECTED = 1
+
+
+class GeoParams(ctypes.Structure):
+    """gw_geo_params_t (include/graphwalk.h); struct_size is filled in by default."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("symmetrize", ctypes.c_int32), ("squared", ctypes.c_int32),
+                ("delta", ctypes.c_double), ("round_cap", ctypes.c_int32)]
+
+    def __init__(self, symmetrize=GEO_SYM_UNION, squared=0, delta=0.0, round_cap=0):
+        super().__init__(ctypes.sizeof(GeoParams), symmetrize, int(squared), delta, int(round_cap))
+
+
+class GeoStats(ctypes.Structure):
+    """gw_geo_stats_t."""
+    _fields_ = [("entries", ctypes.c_int64), ("components", ctypes.c_int64), ("main_component_size", ctypes.c_int64),
+                ("rounds_max", ctypes.c_int64), ("relaxations", ctypes.c_int64), ("fallbacks", ctypes.c_int32)]
 
 
 LE_SYM_MEAN = 0
@@ -345,6 +365,16 @@ SIGNATURES = {
     "gw_nng_query": (ctypes.c_int, [P, P, I64, P, P, P, P]),
     "gw_nng_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
     "gw_nng_tiles": (ctypes.c_int, [P, PI32, PI32, PI32, PI32]),
+    "gw_geo_create": (ctypes.c_int, [ctypes.c_int, I64, ctypes.POINTER(GeoParams), PP]),
+    "gw_geo_free": (ctypes.c_int, [P]),
+    "gw_geo_last_error": (CP, [P]),
+    "gw_geo_set_rows": (ctypes.c_int, [P, P, P, ctypes.c_int]),
+    "gw_geo_set_csr": (ctypes.c_int, [P, P, P, P]),
+    "gw_geo_components": (ctypes.c_int, [P, P, PI32]),
+    "gw_geo_query": (ctypes.c_int, [P, P, I64, P, I64, P]),
+    "gw_geo_stats": (ctypes.c_int, [P, ctypes.POINTER(GeoStats)]),
+    "gw_geo_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
+    "gw_geo_tiles": (ctypes.c_int, [P, PI32, PI32, PI32]),
     "gw_le_create": (ctypes.c_int, [ctypes.c_int, I64, ctypes.POINTER(LeParams), PP]),
     "gw_le_free": (ctypes.c_int, [P]),
     "gw_le_last_error": (CP, [P]),
@@ -384,14 +414,16 @@ def lib():
     return _lib
 
 
-def check(rc, handle=None, sgns=None, deepsim=None, ovr=None, knn=None, le=None, sdne=None, nng=None):
+def check(rc, handle=None, sgns=None, deepsim=None, ovr=None, knn=None, le=None, sdne=None, nng=None, geo=None):
     """Raise for a failing status; `handle` a gw_graph, `sgns` a gw_sgns, `deepsim` a gw_deepsim or True for a
-    handle-less gw_deepsim call, `ovr`, `knn`, `le`, `sdne` and `nng` likewise for gw_ovr, gw_knn, gw_le, gw_sdne and
-    gw_nng (for the message)."""
+    handle-less gw_deepsim call, `ovr`, `knn`, `le`, `sdne`, `nng` and `geo` likewise for gw_ovr, gw_knn, gw_le, gw_sdne,
+    gw_nng and gw_geo (for the message)."""
     if rc == GW_OK:
         return
     L = lib()
-    if nng is not None:
+    if geo is not None:
+        msg = L.gw_geo_last_error(None if geo is True else geo)
+    elif nng is not None:
         msg = L.gw_nng_last_error(None if nng is True else nng)
     elif sdne is not None:
         msg = L.gw_sdne_last_error(None if sdne is True else sdne)

@@ -52,6 +52,7 @@ extern "C" {
 #define GW_ERR_KEY (-9)         /* missing edge key (Python KeyError)          */
 #define GW_ERR_ZERODIV (-10)    /* weights sum to 0 (ZeroDivisionError)        */
 #define GW_ERR_CAPACITY (-11)   /* workspace too small for the frontier        */
+#define GW_ERR_INTERNAL (-12)   /* a bounded device loop ended unfinished      */
 
 /* ---- graph semantics ------------------------------ */
 /* networkx simple graph as built by read_graph (node2vec/src/main.py:76-89):
@@ -1100,6 +1101,86 @@ int gw_nng_kernel_attrs(gw_nng* m, int cap, const char** names, int32_t* vgprs, 
  * columns per LDS chunk, buf = entries of a row's candidate buffer for this
  * handle's topk.  GW_ERR_STATE for a host handle.                             */
 int gw_nng_tiles(const gw_nng* m, int32_t* tq, int32_t* tc, int32_t* kc, int32_t* buf);
+
+/* ---- geodesics on a sparse graph -------------------------------------------- */
+/* Isomap's hot path (the method IsoMap_LE's README names first): shortest-path
+ * distances from many sources over a sparse graph with non-negative fp64
+ * lengths, for full Isomap (every vertex a source) and landmark Isomap (L << n
+ * sources).  csrc/gw_geo_law.h holds the one definition the kernels and the host
+ * evaluation (device = -1) share; they agree bit for bit (tested).
+ *   rows        top-k rows as gw_le_set_rows takes them, or a CSR: an id of -1 ends
+ *               a row, an id equal to its row is dropped, a value that is NaN,
+ *               negative or +inf is dropped, -0.0 counts as +0.0, a repeated id
+ *               keeps the smallest value, an id outside [-1, n) gives GW_ERR_RANGE;
+ *   squared     1: the values are squared distances (gw_nng_query's out_d2) and the
+ *               length is their square root, taken on the host while the graph is
+ *               assembled; 0: the values are the lengths;
+ *   symmetrize  GW_GEO_SYM_UNION: l_ij = min of the listed a_ij and a_ji, an edge
+ *               listed one way stands both ways; GW_GEO_DIRECTED: as listed;
+ *   distance    dist(s, s) = +0; dist(s, v) = the minimum over all paths of the
+ *               lengths added left to right from +0; +inf where there is no path or
+ *               where every path's sum overflows.  Rounding of + is monotone and the
+ *               lengths are >= 0, so this minimum is the only fixed point of
+ *               dist[v] = min(dist[v], dist[u] + l(u,v)): no schedule changes a bit;
+ *   components  of the symmetrised graph; a component's id is its lowest vertex, the
+ *               main component is the largest, the lowest id winning ties.
+ * Limits: n < 2^31.                                                            */
+#define GW_GEO_SYM_UNION 0
+#define GW_GEO_DIRECTED 1
+typedef struct gw_geo gw_geo;
+typedef struct gw_geo_params_t {
+  int32_t struct_size; /* as gw_sgns_params_t.struct_size                      */
+  int32_t symmetrize;  /* GW_GEO_SYM_UNION (default) | GW_GEO_DIRECTED         */
+  int32_t squared;     /* 1: values are squared lengths; 0 (default): lengths  */
+  double delta;        /* bucket width of the device schedule; 0 (default) =
+                          chosen from the mean edge length; it never changes a
+                          result; negative or NaN: GW_ERR_INVALID              */
+  int32_t round_cap;   /* measurement aid of the tests: 0 (default) = the device
+                          schedule's own round cap; c > 0: cap = c - 1 (1: every
+                          source ends as Bellman-Ford, counted in fallbacks); it
+                          never changes a result                               */
+} gw_geo_params_t;
+typedef struct gw_geo_stats_t {
+  int64_t entries;             /* directed entries of the assembled graph      */
+  int64_t components;
+  int64_t main_component_size;
+  int64_t rounds_max;          /* most rounds any source of the last query took
+                                  (device; 0 on the host)                      */
+  int64_t relaxations;         /* entries read by the last query, all sources  */
+  int32_t fallbacks;           /* sources that reached the round cap and ended
+                                  as plain Bellman-Ford (device)               */
+} gw_geo_stats_t;
+/* device >= 0: a GPU; -1: the host evaluation.  n = vertices                    */
+int gw_geo_create(int device, int64_t n, const gw_geo_params_t* params, gw_geo** out);
+int gw_geo_free(gw_geo* m);
+const char* gw_geo_last_error(const gw_geo* m);
+/* Host pointers in both modes: the graph is assembled on the host and, for a
+ * device handle, uploaded.  values == NULL in gw_geo_set_csr: every value 1.     */
+int gw_geo_set_rows(gw_geo* m, const int32_t* ids, const double* values, int topk);
+int gw_geo_set_csr(gw_geo* m, const int64_t* offsets, const int32_t* nbrs, const double* values);
+/* component_of[n] (host, may be NULL) and the main component's id (may be NULL) */
+int gw_geo_components(gw_geo* m, int32_t* component_of, int32_t* main_component);
+/* out[r * pitch + v] = dist(sources[r], v), r < nsrc, v < n; pitch >= n and the
+ * columns n .. pitch-1 are not touched.  Pointers are device memory for
+ * device >= 0 and host memory for -1.  sources == NULL: every vertex, nsrc is
+ * ignored.  Repeated and unordered sources are allowed; nsrc == 0 returns GW_OK and
+ * does nothing.  A source outside [0, n) gives GW_ERR_RANGE and nothing is written.
+ * GW_ERR_STATE before gw_geo_set_*.  Runs on `stream` and synchronises it.  A source
+ * the bounded device schedule left unfinished gives GW_ERR_INTERNAL (never seen;
+ * the bound is proven sufficient in csrc/gw_geo.hip).                           */
+int gw_geo_query(gw_geo* m, const int32_t* sources, int64_t nsrc, double* out, int64_t pitch, void* stream);
+/* entries, components and main_component_size of the graph; the rest of the last
+ * query                                                                        */
+int gw_geo_stats(gw_geo* m, gw_geo_stats_t* stats);
+/* As gw_ovr_kernel_attrs: this family's kernels only                          */
+int gw_geo_kernel_attrs(gw_geo* m, int cap, const char** names, int32_t* vgprs, int32_t* scratch_bytes,
+                        int32_t* lds_bytes, int32_t* count);
+/* lanes = threads of a workgroup (one workgroup per source; a lane scans 64
+ * vertices of the bitmap per trip), lds_rows = the largest n whose distance row
+ * and bitmaps are kept in LDS (above it they lie in the source's output row and
+ * in device scratch), sources_per_launch = the grid's bound (a workgroup takes
+ * further sources by stride).  GW_ERR_STATE for a host handle.                  */
+int gw_geo_tiles(const gw_geo* m, int32_t* lanes, int32_t* lds_rows, int32_t* sources_per_launch);
 
 /* ---- multi-GPU exchange (RCCL over xGMI) ---------------------------------- */
 /* the graph is replicated and units (walks, TopSim sources) are
