@@ -114,6 +114,8 @@ int gw_graph_load_edgelist(const char* path, const char* delim, int semantics, i
   *out = nullptr;
   if (semantics == GW_SEM_JAVA_MULTI && (weighted || directed))
     return gw_fail(nullptr, GW_ERR_UNSUPPORTED, "JAVA_MULTI graphs are undirected and unweighted (Graph.java:12)");
+  if (semantics == GW_SEM_JAVA_WGRAPH && directed)
+    return gw_fail(nullptr, GW_ERR_UNSUPPORTED, "JAVA_WGRAPH graphs are undirected (WGraph.java:17)");
   gw_graph* g = new gw_graph();
   int rc = gw_load_edgelist_impl(g, path, delim, semantics, directed, weighted, vcount);
   if (rc != GW_OK) {
@@ -136,6 +138,9 @@ int gw_graph_from_edges(int64_t m, const int64_t* src, const int64_t* dst, const
   else if (semantics == GW_SEM_JAVA_MULTI)
     rc = (w || directed) ? gw_fail(g, GW_ERR_UNSUPPORTED, "JAVA_MULTI graphs are undirected and unweighted")
                          : gw_build_java_multi(g, m, src, dst, vcount);
+  else if (semantics == GW_SEM_JAVA_WGRAPH)
+    rc = directed ? gw_fail(g, GW_ERR_UNSUPPORTED, "JAVA_WGRAPH graphs are undirected (WGraph.java:17)")
+                  : gw_build_java_wgraph(g, m, src, dst, w, vcount);
   else
     rc = gw_fail(g, GW_ERR_INVALID, "unknown semantics %d", semantics);
   if (rc != GW_OK) {
@@ -231,7 +236,7 @@ int gw_graph_info(const gw_graph* g, gw_graph_info_t* info) {
   info->edge_alias_entries = g->edge_alias_entries;
   info->semantics = g->semantics;
   info->directed = g->directed;
-  info->weighted = g->weighted;
+  info->weighted = gw_has_weights(g) ? 1 : 0;  // a JAVA_WGRAPH handle keeps its weights beside the CSR
   info->device = g->device;
   info->sampler_bytes = (g->d.bs_nbr ? g->bitset_words * 4 + g->nnz * (int64_t)sizeof(gw_bs_nbr) : 0) +
                         (g->d.sent ? g->nnz * (int64_t)sizeof(gw_ts_ent) : 0) +
@@ -247,13 +252,22 @@ int gw_graph_export_csr(const gw_graph* g, int64_t* offsets, int32_t* nbrs, doub
   if (offsets) memcpy(offsets, g->offsets.data(), sizeof(int64_t) * (g->n + 1));
   if (nbrs && g->nnz) memcpy(nbrs, g->nbrs.data(), sizeof(int32_t) * g->nnz);
   if (weights && g->nnz) {
-    if (g->weighted)
-      memcpy(weights, g->weights.data(), sizeof(double) * g->nnz);
+    if (gw_has_weights(g))
+      memcpy(weights, gw_entry_weights(g), sizeof(double) * g->nnz);
     else
       for (int64_t i = 0; i < g->nnz; ++i) weights[i] = 1.0;
   }
   if (labels && g->n) memcpy(labels, g->labels.data(), sizeof(int64_t) * g->n);
   if (node_order && g->n) memcpy(node_order, g->order.data(), sizeof(int32_t) * g->n);
+  return GW_OK;
+}
+
+int gw_graph_export_weight_totals(const gw_graph* g, double* totals) {
+  if (!g) return gw_fail(nullptr, GW_ERR_INVALID, "NULL handle");
+  std::vector<double> t;
+  if (!gw_weight_totals(g, &t)) return gw_fail(nullptr, GW_ERR_STATE, "the graph has no weights");
+  if (g->n > 0 && !totals) return gw_fail(nullptr, GW_ERR_INVALID, "totals is NULL");
+  if (g->n) memcpy(totals, t.data(), sizeof(double) * g->n);
   return GW_OK;
 }
 
@@ -455,6 +469,15 @@ int gw_simrank_naive(gw_graph* g, double C, int iters, double* sim_dev, void* st
   if (g->directed) return ret(g, gw_fail(g, GW_ERR_UNSUPPORTED, "naive SimRank needs an undirected graph"));
   if (iters < 0 || (g->n > 0 && !sim_dev)) return ret(g, gw_fail(g, GW_ERR_INVALID, "bad arguments"));
   return ret(g, gw_dev_simrank_naive(g, C, iters, sim_dev, stream));
+}
+
+int gw_simrank_weighted(gw_graph* g, double C, int iters, double* sim_dev, void* stream) {
+  if (!g) return gw_fail(nullptr, GW_ERR_INVALID, "NULL handle");
+  GW_GUARD_DEVICE(g, g->device);
+  int rc = gw_wsimrank_check(g, iters, true);
+  if (rc != GW_OK) return rc;
+  if (g->n > 0 && !sim_dev) return gw_fail(g, GW_ERR_INVALID, "bad arguments");
+  return ret(g, gw_dev_simrank_weighted(g, C, iters, sim_dev, stream));
 }
 
 int gw_write_walks_text(const gw_graph* g, const char* path, const int32_t* walks,

@@ -189,6 +189,70 @@ int gw_build_java_multi(gw_graph* g, int64_t m, const int64_t* src,
 }
 
 // ------------------------------------------------------------------------
+// JAVA_WGRAPH builder (WGraph.java:57-67)
+// ------------------------------------------------------------------------
+// addEdge appends to both adjacency lists (the JAVA_MULTI adjacency) and puts
+// w into edges[src][dst] and edges[dst][src]: one value per unordered pair,
+// the last line that names the pair wins whichever way round it was written.
+int gw_build_java_wgraph(gw_graph* g, int64_t m, const int64_t* src,
+                         const int64_t* dst, const double* w, int64_t vcount) {
+  int rc = gw_build_java_multi(g, m, src, dst, vcount);
+  if (rc != GW_OK) return rc;
+  g->semantics = GW_SEM_JAVA_WGRAPH;
+  auto key = [](int64_t a, int64_t b) { return ((uint64_t)std::min(a, b) << 32) | (uint64_t)std::max(a, b); };
+  // (pair, line) sorted: the last line of a pair is its map value
+  std::vector<std::pair<uint64_t, int64_t>> puts((size_t)m);
+  for (int64_t i = 0; i < m; ++i) puts[(size_t)i] = {key(src[i], dst[i]), i};
+  par_sort(puts.begin(), puts.end(), std::less<std::pair<uint64_t, int64_t>>());
+  std::vector<uint64_t> pk;
+  std::vector<double> pv;
+  for (int64_t i = 0; i < m; ++i)
+    if (i + 1 == m || puts[(size_t)i + 1].first != puts[(size_t)i].first) {
+      pk.push_back(puts[(size_t)i].first);
+      pv.push_back(w ? w[puts[(size_t)i].second] : 0.0);  // addEdge(src, dst): 0.0 (:57-59)
+    }
+  auto value = [&](int64_t a, int64_t b) {
+    return pv[(size_t)(std::lower_bound(pk.begin(), pk.end(), key(a, b)) - pk.begin())];
+  };
+  const int64_t n = g->n;
+  g->wg_w.resize((size_t)g->nnz);
+  g->wg_tot.assign((size_t)n, 0.0);
+#pragma omp parallel for schedule(dynamic, 256)
+  for (int64_t v = 0; v < n; ++v) {
+    const int64_t b = g->offsets[v], e = g->offsets[v + 1];
+    for (int64_t k = b; k < e; ++k) g->wg_w[(size_t)k] = value(v, g->nbrs[k]);
+    // the map's values: one per distinct neighbour, summed in ascending id order
+    std::vector<int32_t> ids(g->nbrs.begin() + b, g->nbrs.begin() + e);
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    double t = 0.0;
+    for (int32_t a : ids) t += value(v, a);
+    g->wg_tot[(size_t)v] = t;
+  }
+  return GW_OK;
+}
+
+const double* gw_entry_weights(const gw_graph* g) {
+  if (g->semantics == GW_SEM_JAVA_WGRAPH) return g->wg_w.data();
+  return g->weighted ? g->weights.data() : nullptr;
+}
+
+bool gw_weight_totals(const gw_graph* g, std::vector<double>* totals) {
+  if (g->semantics == GW_SEM_JAVA_WGRAPH) {
+    *totals = g->wg_tot;
+    return true;
+  }
+  if (!g->weighted) return false;
+  totals->assign((size_t)g->n, 0.0);
+  for (int64_t v = 0; v < g->n; ++v) {
+    double t = 0.0;
+    for (int64_t k = g->offsets[v]; k < g->offsets[v + 1]; ++k) t += g->weights[(size_t)k];
+    (*totals)[(size_t)v] = t;
+  }
+  return true;
+}
+
+// ------------------------------------------------------------------------
 // edgelist parsing
 // ------------------------------------------------------------------------
 static bool is_space(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\v' || c == '\f'; }
@@ -254,6 +318,51 @@ static bool parse_py_float(const char* b, const char* e, double* out) {
   double v = strtod(s.c_str(), &end);
   if (end != s.c_str() + s.size()) return false;
   *out = v;
+  return true;
+}
+
+// Java Double.valueOf: String.trim() (every char <= ' '), optional sign, then
+// "NaN", "Infinity", or digits with an optional '.' (digits on at least one
+// side) and an optional exponent, then an optional d D f F suffix (ignored:
+// the value is the double nearest the decimal string).  Hexadecimal
+// floating-point literals are refused (graphwalk.h).
+static bool parse_java_double(const char* b, const char* e, double* out) {
+  while (b < e && (unsigned char)*b <= ' ') ++b;
+  while (e > b && (unsigned char)e[-1] <= ' ') --e;
+  if (b == e) return false;
+  const char* p = b;
+  bool neg = false;
+  if (*p == '+' || *p == '-') neg = (*p++ == '-');
+  const size_t len = (size_t)(e - p);
+  if (len == 3 && memcmp(p, "NaN", 3) == 0) {
+    *out = NAN;
+    return true;
+  }
+  if (len == 8 && memcmp(p, "Infinity", 8) == 0) {
+    *out = neg ? -INFINITY : INFINITY;
+    return true;
+  }
+  const char* q = p;
+  int digits = 0;
+  while (q < e && *q >= '0' && *q <= '9') ++q, ++digits;
+  if (q < e && *q == '.') {
+    ++q;
+    while (q < e && *q >= '0' && *q <= '9') ++q, ++digits;
+  }
+  if (digits == 0) return false;
+  if (q < e && (*q == 'e' || *q == 'E')) {
+    ++q;
+    if (q < e && (*q == '+' || *q == '-')) ++q;
+    int ed = 0;
+    while (q < e && *q >= '0' && *q <= '9') ++q, ++ed;
+    if (ed == 0) return false;
+  }
+  const char* num_end = q;
+  if (q < e && (*q == 'd' || *q == 'D' || *q == 'f' || *q == 'F')) ++q;
+  if (q != e) return false;
+  std::string s(p, num_end);  // validated decimal: strtod reads all of it, correctly rounded
+  const double v = strtod(s.c_str(), nullptr);
+  *out = neg ? -v : v;
   return true;
 }
 
@@ -346,6 +455,19 @@ int gw_load_edgelist_impl(gw_graph* g, const char* path, const char* delim,
       if (lb == end) break;
       split_tokens(lb, se, d.empty() ? std::string(",") : d, toks);
       while (!toks.empty() && toks.back().first == toks.back().second) toks.pop_back();  // trailing empties dropped
+      if (semantics == GW_SEM_JAVA_WGRAPH) {  // WGraph.java:45-52
+        if (toks.size() != 2 && toks.size() != 3)
+          return gw_fail(g, GW_ERR_IO, "%s:%lld: invalid edge file: should be [src, dst] or  [src, dst, w] (WGraph.java:51)", path, (long long)lineno);
+        int64_t a, b;
+        double wv = 0.0;  // addEdge(src, dst): weight 0.0 (:57-59)
+        if (!parse_java_int(toks[0].first, toks[0].second, &a) || !parse_java_int(toks[1].first, toks[1].second, &b) ||
+            (toks.size() == 3 && !parse_java_double(toks[2].first, toks[2].second, &wv)))
+          return gw_fail(g, GW_ERR_PARSE, "%s:%lld: NumberFormatException (WGraph.java:48-50)", path, (long long)lineno);
+        src.push_back(a);
+        dst.push_back(b);
+        wts.push_back(wv);
+        continue;
+      }
       if (toks.size() < 2)
         return gw_fail(g, GW_ERR_PARSE, "%s:%lld: ArrayIndexOutOfBoundsException: line has < 2 fields for separator '%s' (Graph.java:38-39)", path, (long long)lineno, d.c_str());
       int64_t a, b;
@@ -359,6 +481,8 @@ int gw_load_edgelist_impl(gw_graph* g, const char* path, const char* delim,
     return gw_build_nx_simple(g, (int64_t)src.size(), src.data(), dst.data(), weighted ? wts.data() : nullptr, directed);
   if (semantics == GW_SEM_JAVA_MULTI)
     return gw_build_java_multi(g, (int64_t)src.size(), src.data(), dst.data(), vcount);
+  if (semantics == GW_SEM_JAVA_WGRAPH)
+    return gw_build_java_wgraph(g, (int64_t)src.size(), src.data(), dst.data(), wts.data(), vcount);
   return gw_fail(g, GW_ERR_INVALID, "unknown semantics %d", semantics);
 }
 

@@ -159,6 +159,12 @@ struct gw_graph {
   std::vector<int64_t> offsets;  // n+1
   std::vector<int32_t> nbrs;     // nnz
   std::vector<double> weights;   // nnz (empty if unweighted)
+  // GW_SEM_JAVA_WGRAPH only.  `weighted` stays 0 and `weights` empty on such a
+  // handle, so every family that reads those two sees the JAVA_MULTI
+  // multigraph of the adjacency lists; only gw_simrank_weighted, the
+  // accessors and gw_graph_info (which reports weighted = 1) read these.
+  std::vector<double> wg_w;      // nnz: the pair's final map value (WGraph.java:64-65) per adjacency entry
+  std::vector<double> wg_tot;    // n: sum over distinct neighbours, ascending id (WeightedSimRank.java:72-79)
   std::vector<int64_t> labels;   // n (dense id -> original label)
   std::vector<int32_t> order;    // n (G.nodes() order as dense ids)
   // device state
@@ -182,6 +188,17 @@ struct gw_graph {
   int64_t* sr_poff = nullptr;  // [m+1] offsets of the row-padded stream (rows start on 16-entry chunks)
   int32_t* sr_rows = nullptr;  // [m] compact id -> vertex
   int64_t sr_n = 0, sr_m = 0;
+  // weighted SimRank workspace (gw_wsimrank.hip): the same roles over the
+  // 8-entry weighted layout, released by gw_dev_simrank_release too
+  double* wsr_work = nullptr;     // m*m doubles (U = N S)
+  double* wsr_x = nullptr;        // m*m compact S when m < n
+  uint32_t* wsr_ent = nullptr;    // [padded] byte offset of the compact neighbour
+  double* wsr_wt = nullptr;       // [padded] weight of the entry, 0.0 on padding
+  uint16_t* wsr_heads = nullptr;  // [padded / 8] head-of-row bits
+  int64_t* wsr_poff = nullptr;    // [m+1] row starts in the padded stream (multiples of 8)
+  double* wsr_tot = nullptr;      // [m] weight totals of the compact rows
+  int32_t* wsr_rows = nullptr;    // [m] compact id -> vertex
+  int64_t wsr_n = 0, wsr_m = 0;
   std::string err;
 };
 
@@ -213,11 +230,28 @@ int gw_write_sim_sparse_impl(const char* path, const int64_t* begin, const int32
 int gw_fail(gw_graph* g, int code, const char* fmt, ...);
 void gw_set_tls_error(const std::string& s);
 
+// the refusals shared by gw_simrank_weighted and its _host / _ref forms
+inline int gw_wsimrank_check(gw_graph* g, int iters, bool need_device) {
+  if (need_device && g->device < 0) return gw_fail(g, GW_ERR_STATE, "graph is not on a device");
+  if (g->directed) return gw_fail(g, GW_ERR_UNSUPPORTED, "weighted SimRank needs an undirected graph");
+  if (g->semantics != GW_SEM_JAVA_WGRAPH && !g->weighted)
+    return gw_fail(g, GW_ERR_UNSUPPORTED, "the graph has no weights: use gw_simrank_naive");
+  if (iters < 0) return gw_fail(g, GW_ERR_INVALID, "iters must be >= 0");
+  return GW_OK;
+}
+
 // host graph builders (gw_graph_host.cpp)
 int gw_build_nx_simple(gw_graph* g, int64_t m, const int64_t* src,
                        const int64_t* dst, const double* w, int directed);
 int gw_build_java_multi(gw_graph* g, int64_t m, const int64_t* src,
                         const int64_t* dst, int64_t vcount);
+int gw_build_java_wgraph(gw_graph* g, int64_t m, const int64_t* src,
+                         const int64_t* dst, const double* w, int64_t vcount);
+// weighted SimRank inputs of a handle (gw_graph_host.cpp): the weight per
+// adjacency entry (nullptr on an unweighted handle) and the per-vertex totals
+inline bool gw_has_weights(const gw_graph* g) { return g->semantics == GW_SEM_JAVA_WGRAPH || g->weighted; }
+const double* gw_entry_weights(const gw_graph* g);
+bool gw_weight_totals(const gw_graph* g, std::vector<double>* totals);
 
 // device code entry points (gw_*.hip), all return GW_* codes
 int gw_dev_upload(gw_graph* g, int device);
@@ -240,6 +274,8 @@ int gw_dev_topsim_m(gw_graph* g, int variant, int capacity, int sample, int step
                     const int32_t* sources_dev, int64_t nsrc, int32_t* out_keys_dev, float* out_vals_dev,
                     int32_t* out_size_dev, int64_t* stats_dev, void* stream);
 int gw_dev_simrank_naive(gw_graph* g, double C, int iters, double* sim_dev, void* stream);
+int gw_dev_simrank_weighted(gw_graph* g, double C, int iters, double* sim_dev, void* stream);
+void gw_dev_wsimrank_release(gw_graph* g);
 int gw_dev_bitset_build(gw_graph* g, int64_t budget_bytes, bool lists_only = false);
 double gw_bitset_build_model_s(gw_graph* g);
 int gw_dev_walk_bitset_launch(gw_graph* g, int L, uint64_t seed, int64_t walk_begin, int64_t walk_count,

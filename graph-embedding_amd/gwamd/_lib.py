@@ -35,6 +35,8 @@ GW_ERR_INTERNAL = -12
 
 SEM_NX_SIMPLE = 0
 SEM_JAVA_MULTI = 1
+SEM_JAVA_WGRAPH = 2
+SEMANTICS = {"nx": SEM_NX_SIMPLE, "java": SEM_JAVA_MULTI, "wgraph": SEM_JAVA_WGRAPH}
 N2V_REPLAY = 0
 N2V_REJECTION = 1
 N2V_BITSET = 2
@@ -259,6 +261,7 @@ SIGNATURES = {
     "gw_graph_set_options": (ctypes.c_int, [P, ctypes.POINTER(Options)]),
     "gw_graph_get_options": (ctypes.c_int, [P, ctypes.POINTER(Options)]),
     "gw_graph_export_csr": (ctypes.c_int, [P, P, P, P, P, P]),
+    "gw_graph_export_weight_totals": (ctypes.c_int, [P, P]),
     "gw_graph_free": (ctypes.c_int, [P]),
     "gw_graph_to_device": (ctypes.c_int, [P, ctypes.c_int]),
     "gw_n2v_prepare": (ctypes.c_int, [P, D, D, ctypes.c_int]),
@@ -295,6 +298,10 @@ SIGNATURES = {
     "gw_format_java_double": (ctypes.c_int, [D, ctypes.c_char_p, I64]),
     "gw_simrank_naive": (ctypes.c_int, [P, D, ctypes.c_int, P, P]),
     "gw_simrank_naive_host": (ctypes.c_int, [P, D, ctypes.c_int, P]),
+    "gw_simrank_weighted": (ctypes.c_int, [P, D, ctypes.c_int, P, P]),
+    "gw_simrank_weighted_host": (ctypes.c_int, [P, D, ctypes.c_int, P]),
+    "gw_simrank_weighted_ref": (ctypes.c_int, [P, D, ctypes.c_int, ctypes.c_int, P]),
+    "gw_simrank_weighted_kernel_attrs": (ctypes.c_int, [P, P, P, P]),
     "gw_write_walks_text": (ctypes.c_int, [P, CP, P, P, I64, ctypes.c_int]),
     "gw_write_sim_text_dense": (ctypes.c_int, [CP, P, P, I64, I64, ctypes.c_int, CP, ctypes.c_int]),
     "gw_write_sim_text_topk": (ctypes.c_int, [CP, P, P, P, I64, ctypes.c_int, CP, ctypes.c_int]),

@@ -12,6 +12,7 @@ class GWGraph:
     Construction mirrors the two reference graph semantics:
       * `from_edgelist(..., semantics="nx")`  == read_graph (node2vec/src/main.py:76-89)
       * `from_edgelist(..., semantics="java")` == structures.Graph(path, V) (Graph.java:28-42)
+      * `from_edgelist(..., semantics="wgraph")` == structures.WGraph(path, V) (WGraph.java:35-54)
     """
 
     def __init__(self, handle):
@@ -22,7 +23,7 @@ class GWGraph:
     @classmethod
     def from_edgelist(cls, path, delimiter=None, semantics="nx", directed=False,
                       weighted=False, vcount=-1):
-        sem = C.SEM_NX_SIMPLE if semantics == "nx" else C.SEM_JAVA_MULTI
+        sem = C.SEMANTICS.get(semantics, C.SEM_JAVA_MULTI)
         h = ctypes.c_void_p()
         d = None if delimiter is None else delimiter.encode()
         rc = C.lib().gw_graph_load_edgelist(str(path).encode(), d, sem, int(directed),
@@ -35,7 +36,7 @@ class GWGraph:
         src = np.ascontiguousarray(src, dtype=np.int64)
         dst = np.ascontiguousarray(dst, dtype=np.int64)
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
-        sem = C.SEM_NX_SIMPLE if semantics == "nx" else C.SEM_JAVA_MULTI
+        sem = C.SEMANTICS.get(semantics, C.SEM_JAVA_MULTI)
         h = ctypes.c_void_p()
         rc = C.lib().gw_graph_from_edges(len(src), C.ptr(src), C.ptr(dst), C.ptr(w), sem,
                                          int(directed), int(vcount), ctypes.byref(h))
@@ -50,7 +51,7 @@ class GWGraph:
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
         lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int64)
         order = None if node_order is None else np.ascontiguousarray(node_order, dtype=np.int32)
-        sem = C.SEM_NX_SIMPLE if semantics == "nx" else C.SEM_JAVA_MULTI
+        sem = C.SEMANTICS.get(semantics, C.SEM_JAVA_MULTI)
         h = ctypes.c_void_p()
         rc = C.lib().gw_graph_from_csr(len(offsets) - 1, C.ptr(offsets), C.ptr(nbrs), C.ptr(w),
                                        C.ptr(lab), C.ptr(order), sem, int(directed), ctypes.byref(h))
@@ -141,6 +142,13 @@ class GWGraph:
         C.check(C.lib().gw_graph_export_csr(self._h, C.ptr(offs), C.ptr(nbrs), C.ptr(w), C.ptr(lab),
                                             C.ptr(order)), self._h)
         return dict(offsets=offs, nbrs=nbrs, weights=w, labels=lab, node_order=order)
+
+    def export_weight_totals(self):
+        """The per-vertex weight totals gw_simrank_weighted divides by
+        (StateError on an unweighted handle)."""
+        t = np.empty(self.info().n, np.float64)
+        C.check(C.lib().gw_graph_export_weight_totals(self._h, C.ptr(t)), self._h)
+        return t
 
     def to_device(self, device=0):
         C.check(C.lib().gw_graph_to_device(self._h, int(device)), self._h)

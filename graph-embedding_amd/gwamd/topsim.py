@@ -12,6 +12,8 @@
 and `SingleRandomWalk` (SingleRandomWalk.java) use the same kernel.
 `SimRank` (SimRank.java, the naive all-pairs ground truth) runs on the GPU
 as two sparse row-gather passes per round; `printByOrderAll` is its writer.
+`WGraph` (WGraph.java) and `WeightedSimRank` (WeightedSimRank.java) are the
+weighted pair: the same two passes with a weight per adjacency entry.
 
 Randomness: the reference draws from an unseeded static java.util.Random
 (Graph.java:17); here every random child is a Philox draw keyed by
@@ -61,6 +63,34 @@ class Graph:
 
     def getECount(self):
         return self.eCount
+
+
+class WGraph(Graph):
+    """structures.WGraph (WGraph.java:22-126): the multigraph of the first two
+    fields of every line plus one weight per unordered pair (the last line
+    naming the pair wins, both ways round; a 2-field line sets 0.0).  Every
+    TopSim / SimRank class takes it as the `Graph` of its adjacency lists
+    (WGraph.randNeighbor is uniform over them); WeightedSimRank reads the
+    weights."""
+
+    def __init__(self, graphPath, V, separator=SEPARATOR, device=0):
+        self.vCount = int(V)
+        self._g = GWGraph.from_edgelist(graphPath, delimiter=separator, semantics="wgraph", vcount=int(V))
+        csr = self._g.export_csr()
+        self._offs = csr["offsets"]
+        self._nbrs = csr["nbrs"]
+        self._wts = csr["weights"]                      # the pair's map value, once per adjacency entry
+        self._totals = self._g.export_weight_totals()   # sum of a vertex's map values
+        self.eCount = len(self._nbrs) // 2
+        self.device = device
+        self._on_device = False
+
+    def getAllEdgeWeight(self, u):
+        """edges[u] (WGraph.java:69-71): {neighbour: weight}."""
+        b, e = self._offs[u], self._offs[u + 1]
+        return dict(zip(self._nbrs[b:e].tolist(), self._wts[b:e].tolist()))
+
+    edges = getAllEdgeWeight                            # WGraph.java:116-118
 
 
 class _TopSimBase:
@@ -420,6 +450,66 @@ class SimRank:
         return self._sim
 
 
+class WeightedSimRank:
+    """simrank.weighted.WeightedSimRank (WeightedSimRank.java:19-98): naive
+    SimRank with edge weights over a WGraph, STEP = 50 rounds (the reference's
+    private field; `step` overrides it).  getResult() is the dense V x V
+    matrix with a zero diagonal.  No guards, as in the reference: a vertex
+    whose weights sum to 0 gives NaN / Inf.  Needs V*V doubles on the device."""
+    STEP = 50
+
+    def __init__(self, wg, C_=C_DEFAULT, step=None):
+        self.wg = wg
+        self.COUNT = wg.getVCount()
+        self.C = float(C_)
+        self.STEP = WeightedSimRank.STEP if step is None else int(step)
+        self._sim = None
+
+    def compute(self):
+        import torch
+        wg = self.wg
+        wg._ensure_device()
+        dev = torch.device("cuda", wg.device)
+        sim = torch.empty((self.COUNT, self.COUNT), dtype=torch.float64, device=dev)
+        h = wg._g.handle
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        C.check(C.lib().gw_simrank_weighted(h, self.C, self.STEP, C.ptr(sim), stream), h)
+        self._sim = sim.cpu().numpy()
+
+    def sim(self, v, w):
+        """WeightedSimRank.java:68-93: one round for the pair (v, w) from the
+        current matrix (the identity before compute()), on the host: the double
+        loop's sum taken over the summed entry weights of v and w."""
+        if v == w:
+            return 1.0
+        wg = self.wg
+        if wg.degree(v) == 0 or wg.degree(w) == 0:
+            return 0.0
+        S = self._sim if self._sim is not None else np.eye(self.COUNT)
+        nv = np.zeros(self.COUNT)
+        nw = np.zeros(self.COUNT)
+        np.add.at(nv, wg.neighbors(v), wg._wts[wg._offs[v]:wg._offs[v + 1]])
+        np.add.at(nw, wg.neighbors(w), wg._wts[wg._offs[w]:wg._offs[w + 1]])
+        result = float(nv @ S @ nw)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return float(np.float64(self.C * result) / np.float64(wg._totals[v] * wg._totals[w]))
+
+    def getResult(self):
+        if self._sim is None:
+            raise RuntimeError("call compute() first")
+        return self._sim
+
+    def kernel_attrs(self):
+        """{instantiation: {vgprs, scratch_bytes, lds_bytes}} of the weighted gather kernel."""
+        self.wg._ensure_device()
+        v, s, l = (np.zeros(4, np.int32) for _ in range(3))
+        h = self.wg._g.handle
+        C.check(C.lib().gw_simrank_weighted_kernel_attrs(h, C.ptr(v), C.ptr(s), C.ptr(l)), h)
+        names = ("lds_row_pass1", "hbm_row_pass1", "lds_row_pass2", "hbm_row_pass2")
+        return {k: {"vgprs": int(v[i]), "scratch_bytes": int(s[i]), "lds_bytes": int(l[i])}
+                for i, k in enumerate(names)}
+
+
 def printByOrderAll(sim, outPath, topk=1000, testTopK=10, separator=SEPARATOR):
     """Print.printByOrderAll (Print.java:55-84): printByOrder with `%.7f`."""
     if isinstance(sim, SimRank):
@@ -430,9 +520,12 @@ def printByOrderAll(sim, outPath, topk=1000, testTopK=10, separator=SEPARATOR):
 def printByOrder(sim, outPath, topk=TOPK, testTopK=None, separator=SEPARATOR, decimals=6):
     """Print.printByOrder (Print.java:25-53): `outPath` gets "v,id,...\\r\\n" and
     `outPath.sim.txt` gets "v,id:%.6f,...\\r\\n".  `sim` is a dense V x V array
-    (exact Java FixedMaxPQ tie order and %.6f HALF_UP), a TopSim object, or a
+    (exact Java FixedMaxPQ tie order and %.6f HALF_UP), a WeightedSimRank (its
+    getResult()), a TopSim object, or a
     TopSim_M object (the FixedCacheMap[] overload, Print.java:94-124: last
     `topk` entries of each map's ascending iteration)."""
+    if isinstance(sim, WeightedSimRank):   # Print.printByOrder(sr.getResult(), ...) (WeightedSimRank.java:116)
+        sim = sim.getResult()
     if isinstance(sim, _TopSimM):
         src, keys, vals, size = sim.raw()
         C.check(C.lib().gw_write_sim_text_cachemap(

@@ -6,13 +6,17 @@
 //   TopSim_doubleSample        (TopSim_doubleSample.java:30-56)   --algo double
 //   TopSim_Dev                 (TopSim_Dev.java:31-95)            --algo dev
 //   DoubleRandomWalk           (DoubleRandomWalk.java:25-48)      --algo drw
+//   WeightedSimRank.main       (WeightedSimRank.java:101-121)     --algo wsimrank
 //
 //   simrank_variants --graph PATH --V N [--sep ,] --algo A --out PREFIX
 //       [--sample N] [--step N] [--M N] [--topk K] [--single S] [--seed S]
 //
 // simrank writes Print.printByOrderAll(sim, out, 1000, 10); topsim_m / srw_m
 // write Print.printByOrder(FixedCacheMap[], out, TOPK); the dense variants
-// write the V*V doubles to out.bin (dev: candidates from a naive SimRank).
+// write the V*V doubles to out.bin (dev: candidates from a naive SimRank);
+// wsimrank loads the file as a structures.WGraph (third field = weight), runs
+// --step rounds (default: the reference's 50) and writes
+// Print.printByOrder(result, out, 20).
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -34,6 +38,7 @@ static void dump(const std::string& path, const std::vector<double>& v) {
 int main(int argc, char** argv) {
   std::string graph, algo, out = "out", sep = conf::MyConfiguration::SEPARATOR;
   int V = -1, sample = 1000, step = 3, M = 5, single = 1, device = 0;
+  bool step_given = false;
   uint64_t seed = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -50,7 +55,7 @@ int main(int argc, char** argv) {
     else if (a == "--algo") algo = val();
     else if (a == "--out") out = val();
     else if (a == "--sample") sample = atoi(val().c_str());
-    else if (a == "--step") step = atoi(val().c_str());
+    else if (a == "--step") { step = atoi(val().c_str()); step_given = true; }
     else if (a == "--M") M = atoi(val().c_str());
     else if (a == "--topk") conf::MyConfiguration::TOPK = atoi(val().c_str());
     else if (a == "--single") single = atoi(val().c_str());
@@ -63,11 +68,19 @@ int main(int argc, char** argv) {
     }
   }
   if (graph.empty() || V < 0 || algo.empty()) {
-    std::cerr << "usage: " << argv[0] << " --graph PATH --V N --algo simrank|topsim_m|srw_m|double|dev|drw\n";
+    std::cerr << "usage: " << argv[0] << " --graph PATH --V N --algo simrank|topsim_m|srw_m|double|dev|drw|wsimrank\n";
     return 2;
   }
   conf::MyConfiguration::SEPARATOR = sep;
   try {
+    if (algo == "wsimrank") {
+      structures::WGraph wg(graph, V, sep, device);
+      simrank::weighted::WeightedSimRank sr(wg, step_given ? step : 50);
+      sr.compute();
+      utils::Print::printByOrder(sr.getResult(), V, out, conf::MyConfiguration::TOPK,
+                                 conf::MyConfiguration::TOPK);  // :116; TOPK = 20 unless --topk
+      return 0;
+    }
     structures::Graph g(graph, V, sep, device);
     if (algo == "simrank") {
       simrank::SimRank sr(g, step);

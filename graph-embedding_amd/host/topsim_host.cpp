@@ -26,8 +26,12 @@ void check(int rc, const gw_graph* g) {
 
 namespace structures {
 Graph::Graph(const std::string& graphPath, int V, const std::string& separator, int device)
+    : Graph(graphPath, V, separator, device, GW_SEM_JAVA_MULTI) {}
+
+Graph::Graph(const std::string& graphPath, int V, const std::string& separator, int device, int semantics)
     : vCount(V), device_(device) {
-  gw::check(gw_graph_load_edgelist(graphPath.c_str(), separator.c_str(), GW_SEM_JAVA_MULTI, 0, 0, V, &g_));
+  gw::check(gw_graph_load_edgelist(graphPath.c_str(), separator.c_str(), semantics, 0,
+                                   semantics == GW_SEM_JAVA_WGRAPH, V, &g_));
   gw_graph_info_t inf;
   gw::check(gw_graph_info(g_, &inf), g_);
   offsets_.resize(inf.n + 1);
@@ -43,6 +47,23 @@ Graph::~Graph() {
 
 std::vector<int> Graph::neighbors(int v) const {
   return std::vector<int>(nbrs_.begin() + offsets_[v], nbrs_.begin() + offsets_[v + 1]);
+}
+
+WGraph::WGraph(const std::string& graphPath, int V, const std::string& separator, int device)
+    : Graph(graphPath, V, separator, device, GW_SEM_JAVA_WGRAPH) {
+  gw_graph_info_t inf;
+  gw::check(gw_graph_info(handle(), &inf), handle());
+  weights_.resize((size_t)inf.nnz);
+  totals_.resize((size_t)inf.n);
+  gw::check(gw_graph_export_csr(handle(), nullptr, nullptr, weights_.data(), nullptr, nullptr), handle());
+  gw::check(gw_graph_export_weight_totals(handle(), totals_.data()), handle());
+}
+
+std::unordered_map<int, double> WGraph::getAllEdgeWeight(int u) const {
+  std::unordered_map<int, double> m;
+  const std::vector<int> nb = neighbors(u);
+  for (size_t k = 0; k < nb.size(); ++k) m[nb[k]] = entryWeight(u, (int)k);  // one value per neighbour
+  return m;
 }
 }  // namespace structures
 
@@ -156,6 +177,27 @@ double SimRank::sim(int v, int w) const {
   // Java int product (:76): wraps to a signed 32-bit value, multiplied unsigned here (no signed overflow)
   return conf::MyConfiguration::C * result / (int32_t)((uint32_t)dv * (uint32_t)dw);
 }
+
+namespace weighted {
+void WeightedSimRank::compute() {
+  const int64_t V = wg_.getVCount();
+  sim_.assign((size_t)(V * V), 0.0);
+  gw::check(gw_simrank_weighted_host(wg_.handle(), conf::MyConfiguration::C, STEP, sim_.data()), wg_.handle());
+}
+
+double WeightedSimRank::sim(int v, int w) const {
+  if (v == w) return 1;
+  if (wg_.degree(v) == 0 || wg_.degree(w) == 0) return 0;
+  const int64_t V = wg_.getVCount();
+  const std::vector<int> nv = wg_.neighbors(v), nw = wg_.neighbors(w);
+  double result = 0;
+  for (size_t a = 0; a < nv.size(); ++a)
+    for (size_t b = 0; b < nw.size(); ++b)
+      result += wg_.entryWeight(v, (int)a) * wg_.entryWeight(w, (int)b) *
+                (sim_.empty() ? (nv[a] == nw[b] ? 1.0 : 0.0) : sim_[(size_t)nv[a] * V + nw[b]]);
+  return conf::MyConfiguration::C * result / (wg_.totalWeight(v) * wg_.totalWeight(w));  // :92, no guard
+}
+}  // namespace weighted
 }  // namespace simrank
 
 namespace utils {

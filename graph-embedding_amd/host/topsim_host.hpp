@@ -9,6 +9,7 @@
 
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/graphwalk.h"
@@ -54,6 +55,10 @@ class Graph {
   gw_graph* handle() const { return g_; }
   int device() const { return device_; }
 
+ protected:
+  Graph(const std::string& graphPath, int V, const std::string& separator, int device, int semantics);
+  int64_t rowBegin(int v) const { return offsets_[v]; }
+
  private:
   gw_graph* g_ = nullptr;
   int vCount = 0;
@@ -61,6 +66,24 @@ class Graph {
   int device_ = 0;
   std::vector<int64_t> offsets_;
   std::vector<int32_t> nbrs_;
+};
+
+// structures.WGraph (WGraph.java:22-126): the multigraph of the first two
+// fields of every line plus one weight per unordered pair (the last line that
+// names the pair wins, both ways round; a 2-field line sets 0.0).  Every
+// simrank:: class takes it as the Graph of its adjacency lists
+// (WGraph.randNeighbor is uniform over them); WeightedSimRank reads the weights.
+class WGraph : public Graph {
+ public:
+  WGraph(const std::string& graphPath, int V, const std::string& separator = conf::MyConfiguration::SEPARATOR,
+         int device = 0);
+  std::unordered_map<int, double> getAllEdgeWeight(int u) const;                  // :69-71
+  std::unordered_map<int, double> edges(int v) const { return getAllEdgeWeight(v); }  // :116-118
+  double entryWeight(int v, int k) const { return weights_[(size_t)(rowBegin(v) + k)]; }  // of neighbors(v)[k]
+  double totalWeight(int v) const { return totals_[(size_t)v]; }  // sum of the map's values (ascending id)
+
+ private:
+  std::vector<double> weights_, totals_;
 };
 }  // namespace structures
 
@@ -215,6 +238,23 @@ class SimRank {
   int STEP;
   std::vector<double> sim_;
 };
+
+namespace weighted {
+// simrank.weighted.WeightedSimRank (WeightedSimRank.java:19-98) on the GPU.
+class WeightedSimRank {
+ public:
+  explicit WeightedSimRank(structures::WGraph& wg, int step = 50) : wg_(wg), STEP(step) {}  // STEP = 50 (:20)
+  void compute();                                                 // :40-58 + postProcess
+  double sim(int v, int w) const;                                 // :68-93, one round
+  const std::vector<double>& getResult() const { return sim_; }   // :95-97, V*V row-major
+  int getVCount() const { return wg_.getVCount(); }
+
+ private:
+  structures::WGraph& wg_;
+  int STEP;
+  std::vector<double> sim_;
+};
+}  // namespace weighted
 }  // namespace simrank
 
 namespace utils {

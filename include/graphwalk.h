@@ -64,6 +64,20 @@ extern "C" {
  * line appends both directions, duplicates kept, insertion order, ids dense
  * in [0,V), V given by the caller.                                          */
 #define GW_SEM_JAVA_MULTI 1
+/* structures.WGraph (DeepSim/TopSimAll/src/structures/WGraph.java:35-67): the
+ * JAVA_MULTI adjacency of the first two fields of every line (both
+ * directions appended, duplicates kept, insertion order) plus one fp64 weight
+ * per unordered pair: the last line that names the pair, either way round,
+ * sets it for both directions; a 2-field line sets 0.0 (the two-argument
+ * addEdge).  The handle holds that weight once per adjacency entry and one
+ * total per vertex (the sum over its distinct neighbours, ascending id).
+ * Lines have 2 or 3 fields (anything else: GW_ERR_IO); the weight is what
+ * Double.valueOf reads (surrounding whitespace, sign, decimal / exponent
+ * forms, NaN, Infinity, a trailing d D f F) except hexadecimal floating-point
+ * literals, which are refused with GW_ERR_PARSE.  Undirected only.  Every
+ * family other than gw_simrank_weighted sees the JAVA_MULTI multigraph of the
+ * adjacency lists (WGraph.randNeighbor is uniform over them).               */
+#define GW_SEM_JAVA_WGRAPH 2
 
 /* ---- node2vec modes ------------------------------------------------------ */
 /* exact reference replay: per-node AND per-edge alias tables
@@ -185,12 +199,16 @@ int gw_philox4x32(int device, const uint32_t* in, int64_t n, uint32_t* out);
 /* Replaces read_graph (node2vec/src/main.py:76-89, sem NX_SIMPLE) and
  * new structures.Graph(path, V) (Graph.java:28-42, sem JAVA_MULTI).
  * delim: separator string (NULL or "" = any whitespace, as nx delimiter=None).
- * vcount: JAVA_MULTI only (ids must lie in [0,vcount)); pass -1 otherwise.  */
+ * vcount: JAVA_MULTI / JAVA_WGRAPH only (ids must lie in [0,vcount)); pass -1
+ * otherwise.  JAVA_MULTI ignores a third column; JAVA_WGRAPH (new
+ * structures.WGraph(path, V), WGraph.java:35-54) reads it as the weight
+ * whatever `weighted` says, and refuses directed != 0.                      */
 int gw_graph_load_edgelist(const char* path, const char* delim, int semantics,
                            int directed, int weighted, int64_t vcount,
                            gw_graph** out);
 /* Same semantics from in-memory edge arrays (labels for NX_SIMPLE, dense ids
- * for JAVA_MULTI).  w may be NULL (unweighted, every weight 1).             */
+ * for JAVA_MULTI / JAVA_WGRAPH).  w may be NULL (unweighted, every weight 1;
+ * JAVA_WGRAPH: every weight 0.0, the two-argument addEdge).                 */
 int gw_graph_from_edges(int64_t m, const int64_t* src, const int64_t* dst,
                         const double* w, int semantics, int directed,
                         int64_t vcount, gw_graph** out);
@@ -221,6 +239,13 @@ int gw_graph_info(const gw_graph* g, gw_graph_info_t* info);
  * reference's G.nodes() order; NULL ok).                                    */
 int gw_graph_export_csr(const gw_graph* g, int64_t* offsets, int32_t* nbrs,
                         double* weights, int64_t* labels, int32_t* node_order);
+/* totals[n]: the per-vertex weight totals gw_simrank_weighted divides by.
+ * JAVA_WGRAPH: the sum of a vertex's distinct-neighbour weights in ascending
+ * id order (WeightedSimRank.java:72-79 sums a HashMap's values; its iteration
+ * order is not reproduced, the difference is fp64 reassociation).  Weighted
+ * NX_SIMPLE: the sum of the row's weights in row order.  Unweighted handle:
+ * GW_ERR_STATE.                                                             */
+int gw_graph_export_weight_totals(const gw_graph* g, double* totals);
 int gw_graph_free(gw_graph* g);
 
 /* Options of this handle (defaults: all zero, listed = -1); opt NULL resets
@@ -430,6 +455,40 @@ int gw_simrank_naive(gw_graph* g, double C, int iters, double* sim_dev,
                      void* stream);
 /* Host-buffer form (synchronous): sim[n*n].                                 */
 int gw_simrank_naive_host(gw_graph* g, double C, int iters, double* sim);
+
+/* ---- weighted SimRank --------------------------------------------------------- */
+/* Replaces new WeightedSimRank(wg).compute() + getResult()
+ * (simrank/weighted/WeightedSimRank.java:25-58, 95; the reference's STEP = 50):
+ * S := I; `iters` rounds of
+ *   S'[v][w] = C * sum_{a in adjs(v), b in adjs(w)} wt(v,a) wt(w,b) S[a][b]
+ *              / (T[v] * T[w]),
+ * S'[v][v] = 1, 0 when v or w has no adjacency entry; then diag := 0.  wt is
+ * the handle's weight per adjacency entry, T its per-vertex total
+ * (gw_graph_export_weight_totals).  No guards: totals that are 0 give NaN or
+ * +-Inf as IEEE arithmetic does, and they propagate (:92).  Accepts
+ * JAVA_WGRAPH handles and undirected weighted NX_SIMPLE handles; an
+ * unweighted handle is GW_ERR_UNSUPPORTED (use gw_simrank_naive), a directed
+ * one GW_ERR_UNSUPPORTED, iters < 0 GW_ERR_INVALID, a handle that is not on a
+ * device GW_ERR_STATE.  sim_dev: n*n doubles row-major on the graph's device,
+ * symmetric.  The fp64 workspace (two m*m matrices at most, m = vertices with
+ * an adjacency entry) is kept in the handle.  gw_options_t.simrank_hbm_row and
+ * simrank_window apply as they do to gw_simrank_naive.                       */
+int gw_simrank_weighted(gw_graph* g, double C, int iters, double* sim_dev,
+                        void* stream);
+/* Host-buffer form (synchronous): sim[n*n].                                 */
+int gw_simrank_weighted_host(gw_graph* g, double C, int iters, double* sim);
+/* The same two-pass sparse evaluation in fp64 on the host (OpenMP, nthreads
+ * <= 0: the runtime's default): entry order within a row, rows ascending.
+ * Needs no device.  Equal to the kernel up to summation order, not bit for
+ * bit.  sim[n*n].                                                           */
+int gw_simrank_weighted_ref(const gw_graph* g, double C, int iters, int nthreads,
+                            double* sim);
+/* Registers per lane, scratch bytes per lane and static LDS bytes of the four
+ * instantiations of the weighted gather kernel, in the order (LDS row, pass
+ * 1), (HBM row, pass 1), (LDS row, pass 2), (HBM row, pass 2)
+ * (hipFuncGetAttributes on the graph's device; any output may be NULL).      */
+int gw_simrank_weighted_kernel_attrs(gw_graph* g, int32_t vgprs[4], int32_t scratch_bytes[4],
+                                     int32_t lds_bytes[4]);
 
 /* ---- output writers (host) ------------------------------------------------ */
 /* DeepSim save_list format (DeepSim/src/main.py:237-243): one walk per line,
