@@ -22,15 +22,17 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("GW_OFFLOAD_ARCH", "gfx950")
 
 HIP_SRCS = ["gw_n2v.hip", "gw_n2v_bitset.hip", "gw_topsim.hip", "gw_simrank.hip", "gw_topsim_m.hip", "gw_topsim_d.hip",
-            "gw_sgns.hip", "gw_deepsim.hip", "gw_ovr.hip", "gw_knn.hip", "gw_le.hip", "gw_sdne.hip", "gw_nng.hip", "gw_geo.hip", "gw_wsimrank.hip"]
+            "gw_sgns.hip", "gw_deepsim.hip", "gw_ovr.hip", "gw_knn.hip", "gw_le.hip", "gw_sdne.hip", "gw_nng.hip", "gw_geo.hip", "gw_wsimrank.hip",
+            "gw_layout.hip"]
 CXX_SRCS = ["gw_graph_host.cpp", "gw_capi.cpp", "gw_comm.cpp", "gw_sgns_host.cpp", "gw_deepsim_host.cpp",
             "gw_ovr_host.cpp", "gw_knn_host.cpp", "gw_le_host.cpp", "gw_sdne_host.cpp",
-            "gw_nng_host.cpp", "gw_geo_host.cpp", "gw_wsimrank_host.cpp"]
+            "gw_nng_host.cpp", "gw_geo_host.cpp", "gw_wsimrank_host.cpp", "gw_layout_host.cpp"]
 HEADERS = ["gw_internal.h", "gw_philox.h", "gw_device_common.h", "gw_sgns_law.h", "gw_sgns_internal.h",
            "gw_deepsim_law.h", "gw_deepsim_internal.h", "gw_ovr_law.h", "gw_ovr_internal.h",
            "gw_knn_law.h", "gw_knn_internal.h", "gw_le_law.h", "gw_le_internal.h", "gw_sdne_law.h",
            "gw_sdne_internal.h", "gw_nng_law.h", "gw_nng_internal.h", "gw_trainer_fail.h", "gw_trainer_device.h",
-           "gw_pairs_topk.h", "gw_pairs_host.h", "gw_geo_law.h", "gw_geo_internal.h", "gw_simrank_scan.h"]
+           "gw_pairs_topk.h", "gw_pairs_host.h", "gw_geo_law.h", "gw_geo_internal.h", "gw_simrank_scan.h",
+           "gw_layout_law.h", "gw_layout_internal.h"]
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",

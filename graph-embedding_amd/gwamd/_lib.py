@@ -208,6 +208,14 @@ class GeoStats(ctypes.Structure):
                 ("rounds_max", ctypes.c_int64), ("relaxations", ctypes.c_int64), ("fallbacks", ctypes.c_int32)]
 
 
+class LayoutParams(ctypes.Structure):
+    """gw_layout_params_t (include/graphwalk.h); struct_size is filled in by default."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def __init__(self):
+        super().__init__(ctypes.sizeof(LayoutParams), 0)
+
+
 LE_SYM_MEAN = 0
 LE_SYM_MAX = 1
 LE_CONVERGED = 0
@@ -382,6 +390,17 @@ SIGNATURES = {
     "gw_geo_stats": (ctypes.c_int, [P, ctypes.POINTER(GeoStats)]),
     "gw_geo_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
     "gw_geo_tiles": (ctypes.c_int, [P, PI32, PI32, PI32]),
+    "gw_layout_create": (ctypes.c_int, [ctypes.c_int, I64, ctypes.c_int, ctypes.POINTER(LayoutParams), PP]),
+    "gw_layout_free": (ctypes.c_int, [P]),
+    "gw_layout_last_error": (CP, [P]),
+    "gw_layout_set_csr": (ctypes.c_int, [P, P, P, P]),
+    "gw_layout_set_rows": (ctypes.c_int, [P, P, P, ctypes.c_int]),
+    "gw_layout_set_fixed": (ctypes.c_int, [P, P, I64]),
+    "gw_layout_run": (ctypes.c_int, [P, P, ctypes.c_double, ctypes.c_int32, ctypes.c_double, P, PI32]),
+    "gw_layout_step": (ctypes.c_int, [P, P, ctypes.c_double, ctypes.c_double, P, P, P]),
+    "gw_layout_rescale": (ctypes.c_int, [P, P, ctypes.c_double, P, P]),
+    "gw_layout_kernel_attrs": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(CP), PI32, PI32, PI32, PI32]),
+    "gw_layout_tiles": (ctypes.c_int, [P, PI32, PI32, PI32, PI32]),
     "gw_le_create": (ctypes.c_int, [ctypes.c_int, I64, ctypes.POINTER(LeParams), PP]),
     "gw_le_free": (ctypes.c_int, [P]),
     "gw_le_last_error": (CP, [P]),
@@ -421,14 +440,17 @@ def lib():
     return _lib
 
 
-def check(rc, handle=None, sgns=None, deepsim=None, ovr=None, knn=None, le=None, sdne=None, nng=None, geo=None):
+def check(rc, handle=None, sgns=None, deepsim=None, ovr=None, knn=None, le=None, sdne=None, nng=None, geo=None,
+          layout=None):
     """Raise for a failing status; `handle` a gw_graph, `sgns` a gw_sgns, `deepsim` a gw_deepsim or True for a
     handle-less gw_deepsim call, `ovr`, `knn`, `le`, `sdne`, `nng` and `geo` likewise for gw_ovr, gw_knn, gw_le, gw_sdne,
-    gw_nng and gw_geo (for the message)."""
+    gw_nng and gw_geo, and `layout` for gw_layout (for the message)."""
     if rc == GW_OK:
         return
     L = lib()
-    if geo is not None:
+    if layout is not None:
+        msg = L.gw_layout_last_error(None if layout is True else layout)
+    elif geo is not None:
         msg = L.gw_geo_last_error(None if geo is True else geo)
     elif nng is not None:
         msg = L.gw_nng_last_error(None if nng is True else nng)

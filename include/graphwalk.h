@@ -1241,6 +1241,71 @@ int gw_geo_kernel_attrs(gw_geo* m, int cap, const char** names, int32_t* vgprs, 
  * further sources by stride).  GW_ERR_STATE for a host handle.                  */
 int gw_geo_tiles(const gw_geo* m, int32_t* lanes, int32_t* lds_rows, int32_t* sources_per_launch);
 
+/* ---- spring layout of a graph ------------------------------------------------ */
+/* The layout under IsoMap_LE/simRank.py:show's picture: the Fruchterman-Reingold
+ * force simulation networkx's spring_layout runs (its dense _fruchterman_reingold,
+ * fp64), stated for a sparse matrix.  csrc/gw_layout_law.h holds the one
+ * definition, every order of summation included, that the kernels and the host
+ * evaluation (device = -1) share; they agree bit for bit (tested).
+ *   matrix   a CSR or top-k rows as gw_le_set_rows takes them, used as listed (no
+ *            symmetrisation): an id of -1 ends a row, an id equal to its row is
+ *            dropped, repeated ids add, a negative value repels, a value that is
+ *            not finite gives GW_ERR_INVALID, an id outside [-1, n) GW_ERR_RANGE;
+ *   iteration  disp_i = sum_j (pos_i - pos_j) k^2 / max(d2_ij, 1e-4)
+ *                     - sum_{e in row i} (pos_i - pos_e) a_e max(sqrt(d2), 0.01) / k;
+ *            len_i = |disp_i|, replaced by 0.1 where below 0.01; pos_i += disp_i t / len_i
+ *            (not for a fixed vertex); t -= dt; stop when sqrt(sum step^2) / n < threshold;
+ *   cooling  t0 = 0.1 max(extent of coordinate 0, extent of coordinate 1),
+ *            dt = t0 / (iterations + 1).
+ * Limits: n < 2^31, dim 2 or 3.  A device handle holds ceil(n / 1024) * n * dim
+ * doubles of scratch (the all-pairs kernel's chunk sums): 157 MB at n = 100,000
+ * and dim 2, 15.6 GB at n = 1,000,000; gw_layout_create gives GW_ERR_NOMEM
+ * when it does not fit.                                                         */
+typedef struct gw_layout gw_layout;
+typedef struct gw_layout_params_t {
+  int32_t struct_size; /* as gw_sgns_params_t.struct_size                      */
+  int32_t reserved;    /* 0                                                    */
+} gw_layout_params_t;
+/* device >= 0: a GPU; -1: the host evaluation.  n = vertices, dim = 2 or 3 (else
+ * GW_ERR_INVALID)                                                              */
+int gw_layout_create(int device, int64_t n, int dim, const gw_layout_params_t* params, gw_layout** out);
+int gw_layout_free(gw_layout* m);
+const char* gw_layout_last_error(const gw_layout* m);
+/* Host pointers in both modes: the matrix is checked on the host and, for a device
+ * handle, uploaded.  values == NULL in gw_layout_set_csr: every value 1.          */
+int gw_layout_set_csr(gw_layout* m, const int64_t* offsets, const int32_t* nbrs, const double* values);
+int gw_layout_set_rows(gw_layout* m, const int32_t* ids, const double* values, int topk);
+/* ids[count] (host): the vertices that do not move; count == 0 clears the list.
+ * An id outside [0, n) gives GW_ERR_RANGE.                                      */
+int gw_layout_set_fixed(gw_layout* m, const int32_t* ids, int64_t count);
+/* pos[n][dim], updated in place: device memory for device >= 0, host memory for
+ * -1.  k == 0: sqrt(1.0 / n); k < 0 or NaN, threshold NaN, iterations < 0 give
+ * GW_ERR_INVALID; iterations == 0 leaves pos untouched.  The iterations are
+ * launched back to back on `stream`; once the stop test has set a device flag every
+ * later launch exits at once, and the host reads the count once at the end.
+ * *iterations_done (may be NULL) = iterations carried out.  Synchronises the stream.  GW_ERR_STATE before gw_layout_set_*.            */
+int gw_layout_run(gw_layout* m, double* pos, double k, int32_t iterations, double threshold, void* stream,
+                  int32_t* iterations_done);
+/* One iteration at temperature t, without the cooling and the stop test:
+ * disp_out[n][dim] (may be NULL) = disp, pos_out[n][dim] = pos_in + step.  pos_out
+ * must not be pos_in.  Pointers as in gw_layout_run.  Synchronises the stream.    */
+int gw_layout_step(gw_layout* m, const double* pos_in, double k, double t, double* disp_out, double* pos_out,
+                   void* stream);
+/* networkx's rescale_layout and the shift that follows it: subtract the column
+ * means, multiply by scale / max|pos| where that maximum is > 0, add center[dim]
+ * (host memory in both modes; NULL: zeros).  pos as in gw_layout_run.
+ * Synchronises the stream.                                                      */
+int gw_layout_rescale(gw_layout* m, double* pos, double scale, const double* center, void* stream);
+/* As gw_ovr_kernel_attrs: this family's kernels only                          */
+int gw_layout_kernel_attrs(gw_layout* m, int cap, const char** names, int32_t* vgprs, int32_t* scratch_bytes,
+                           int32_t* lds_bytes, int32_t* count);
+/* rows = rows of a workgroup of the all-pairs kernel (one per thread), chunk = the
+ * law's column chunk (a workgroup streams one chunk through LDS), strands = the
+ * interleaved partial sums of a chunk, block = vertices of a block in the law's
+ * sums over vertices.  The last three are the law's constants: also for a host
+ * handle, where rows is 0.                                                      */
+int gw_layout_tiles(const gw_layout* m, int32_t* rows, int32_t* chunk, int32_t* strands, int32_t* block);
+
 /* ---- multi-GPU exchange (RCCL over xGMI) ---------------------------------- */
 /* the graph is replicated and units (walks, TopSim sources) are
  * sharded by global index with no data-path collective; the only exchange is
